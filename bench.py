@@ -10,9 +10,20 @@ for the three task decoders (they live in un-vendored mmseg/mmdet/mmrotate; SURV
     python bench.py --gpus 8 ...          # no launcher environment: starts its own 8 ranks (torch.distributed.run on 127.0.0.1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 ...
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant GEMM kernel family, HIP-event timed on extra steps run right behind the timed
-region, so that `value` times the step alone) and, at N=1, `cpu_baseline` (the oracle -- a CPU port of the reference path -- timed on the
-host cores on bounded samples: BASELINE configs[0] on all threads and on one, the headline model's fwd+bwd on all threads).
+Prints ONE JSON line (rank 0): `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the configuration.  A plain run
+sets up, warms up, times the --steps steps and prints that line, nothing else.  --full adds everything that needs runs of its own:
+`roofline` (dominant GEMM kernel family, HIP-event timed on extra steps run right behind the timed region, so that `value` times the step
+alone), `clocks`, `forward_only`, `comm` (N > 1 or MTP_FORCE_COMM=1) and, at N=1, `cpu_baseline` (the oracle -- a CPU port of the reference
+path -- timed on the host cores on bounded samples: BASELINE configs[0] on all threads and on one, the headline model's fwd+bwd on all threads).
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy: the loss, and fixed seeded samples of the four
+feature maps, of the gradient buffer and of the updated parameters (see dump_outputs).  The inputs are seeded, so two builds run with the
+same arguments can be compared output for output.  For that the optimizer runs at learning rate 0 unless --lr says otherwise: the AdamW
+kernels do all their work, but the weights keep their seeded values, so every step computes from the same inputs.  With a real rate
+(--lr 6e-5) the trajectory drifts from run to run: the f32 atomics' reordered sums (1e-7) become sign flips of near-zero gradients, which
+AdamW turns into full updates; after 25 steps the gradients of two runs differ by 0.2 - 0.3 of their maximum.
 """
 import argparse
 import json
@@ -464,6 +475,43 @@ def make_loss_and_grads(heads, chans, device="cuda"):
     return loss_and_grads
 
 
+DUMP_SAMPLE = 1 << 21       # elements per sampled array of --dump-outputs (8 MB in f32): 4 maps + gradients + parameters stay under 64 MB
+
+
+def _dump_sample(t, seed):
+    """an f32 copy of a fixed, seeded sample of DUMP_SAMPLE elements of t (all of t when it is smaller); drawn and gathered on the device,
+    so that no host synchronisation is needed"""
+    v = t.detach().reshape(-1)
+    if v.numel() > DUMP_SAMPLE:
+        g = torch.Generator(device=v.device).manual_seed(seed)
+        v = v.index_select(0, torch.randint(0, v.numel(), (DUMP_SAMPLE,), device=v.device, generator=g))
+    return v.to(torch.float32, copy=True)
+
+
+def keep_feature_samples(loss_and_grads, store):
+    """loss_and_grads that first puts a --dump-outputs sample of each feature map into `store`: the backward may reuse the maps' buffers,
+    so they are sampled while the step runs.  Only the last timed step goes through it."""
+    def wrapped(feats):
+        store[:] = [_dump_sample(f, 100 + i) for i, f in enumerate(feats)]
+        return loss_and_grads(feats)
+    return wrapped
+
+
+def dump_outputs(path, loss, feat_samples, flat):
+    """what the last timed step computed, as .npy files: the loss (f64), the samples of the four feature maps taken during that step, and
+    samples of the gradient buffer and of the parameters the optimizer has just updated (f32, the same indices for both)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {"loss": torch.as_tensor(loss).detach().double().reshape(1)}
+    for i, s in enumerate(feat_samples):
+        out["features_%d_sample" % i] = s
+    out["grads_sample"] = _dump_sample(flat.grad, 11)
+    out["params_sample"] = _dump_sample(flat.data, 11)
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+    return sorted(out)
+
+
 def _hbm_fractions_from_profiles():
     """per-kernel rate against the 8 TB/s HBM peak for the HBM-bound kernels of this workload, from the committed table of
     tools/hbm_fractions.py (rocprofv3 single-stream kernel statistics joined with the PMC passes) -- quoted only when it was taken at the kernel sources
@@ -491,18 +539,29 @@ def main():
                     help="internimage_xl = BASELINE configs[4]'s backbone (use --image-size 512 --batch 8 --no-cpu-baseline)")
     ap.add_argument("--batch", type=int, default=64, help="images per GPU (weak scaling)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, measure everything that takes runs of its own: `roofline` (instrumented GEMM steps), `clocks`, "
+                         "`forward_only`, `comm` (N > 1 or MTP_FORCE_COMM=1) and, at N=1, `cpu_baseline`.  The --no-* switches below and --gemm-shapes / "
+                         "--timer-every act on these; without --full the run times the steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (f32 / f64, under 64 MB: the loss and fixed seeded "
+                         "samples of the feature maps, the gradients and the updated parameters)")
+    ap.add_argument("--lr", type=float, default=0.0,
+                    help="AdamW learning rate of the steps.  0 (default): the optimizer runs every kernel as in training, but the weights keep their seeded "
+                         "values, so every step computes from the same inputs and two runs give the same outputs; 6e-5 = the reference's rate, whose "
+                         "trajectory drifts from run to run (f32 atomics reorder sums, and AdamW turns the sign of a near-zero gradient into a full update)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gemm-timer", action="store_true")
     ap.add_argument("--no-forward-only", dest="forward_only", action="store_false",
                     help="skip the extra pass that times the forward alone (inference mode, no saved activations; SURVEY 8d asks for forward-only "
                          "numbers next to the step).  It runs AFTER the timed region and is reported as `forward_only`, never as `value`")
-    ap.add_argument("--forward-only", dest="forward_only", action="store_true", help="(default since round 4; kept for old command lines)")
+    ap.add_argument("--forward-only", dest="forward_only", action="store_true", help="(default of --full since round 4; kept for old command lines)")
     ap.set_defaults(forward_only=True)
     ap.add_argument("--use-ckpt", action="store_true", help="activation checkpointing (`use_ckpt='True'`, VIT:799-800): every block's forward is recomputed in the "
                     "backward -- the recipe MTP pretrains with at 448^2 (Readme.md:233-240).  The recomputation is NOT counted in the step's flops")
-    ap.add_argument("--gemm-shapes", action="store_true", help="print the per-shape table of the instrumented GEMM launches to stderr")
+    ap.add_argument("--gemm-shapes", action="store_true", help="(--full) print the per-shape table of the instrumented GEMM launches to stderr")
     ap.add_argument("--timer-every", type=int, default=0,
-                    help="0 (default since round 6): no step of the timed region carries per-launch HIP events -- `value` times the step alone; the events behind "
+                    help="(--full) 0 (default since round 6): no step of the timed region carries per-launch HIP events -- `value` times the step alone; the events behind "
                          "`roofline` (one stream) and `roofline.concurrent` (as the step runs) are recorded on extra steps right AFTER the timed region.  N > 0: "
                          "additionally instrument every N-th timed step the old way (two events per GEMM launch cost ~1.3 ms per instrumented step)")
     ap.add_argument("--host-input", action="store_true", help="additionally time the step fed from HOST uint8 batches (pinned staging, side-stream H2D, "
@@ -524,6 +583,7 @@ def main():
     ap.add_argument("--cpu-standin", action="store_true",
                     help="TEST ONLY: gloo ranks on CPU exercising the launcher / rendezvous / comm-report plumbing without kernels (prints `standin: true`)")
     args = ap.parse_args()
+    gemm_timer = args.full and not args.no_gemm_timer
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")     # dmabuf IPC: RCCL across processes needs it on this driver (read when HIP initialises)
     os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")              # see mtp_amd/__init__.py
@@ -565,9 +625,9 @@ def main():
     force_comm = os.environ.get("MTP_FORCE_COMM") == "1"     # debugging aid: run the RCCL path on a single GPU
     rccl_log = None
     if world > 1 or force_comm:
-        # what RCCL chose (algorithm / protocol / channels) goes into `comm.rccl`: rank 0's INFO log, written to a file and parsed after the run.  The image
+        # what RCCL chose (algorithm / protocol / channels) goes into `comm.rccl` (--full): rank 0's INFO log, written to a file and parsed after the run.  The image
         # exports NCCL_DEBUG=VERSION (round 5: that is why `rccl` was null in the first forced-comm lines); a level the user picked for a real log stays.
-        if os.environ.get("NCCL_DEBUG", "").upper() in ("", "VERSION", "WARN") and os.environ.get("MTP_RCCL_LOG", "1") != "0":
+        if args.full and os.environ.get("NCCL_DEBUG", "").upper() in ("", "VERSION", "WARN") and os.environ.get("MTP_RCCL_LOG", "1") != "0":
             import tempfile
             rccl_log = os.path.join(tempfile.gettempdir(), "mtp_rccl_%d.%d.log" % (os.getpid(), rank))
             os.environ["NCCL_DEBUG"] = "INFO"
@@ -605,7 +665,7 @@ def main():
                 p.normal_(0, 0.02)
     net = net.cuda().train()
     fdt = torch.bfloat16 if args.precision == "bf16" else torch.float32
-    trainer = DataParallelTrainer(net, lr=6e-5, weight_decay=0.05, max_norm=5.0, total_steps=1000, feature_dtype=fdt,
+    trainer = DataParallelTrainer(net, lr=args.lr, weight_decay=0.05, max_norm=5.0, total_steps=1000, feature_dtype=fdt,
                                   comm_mode=args.comm_mode, comm_bf16=args.comm_bf16)
     torch.manual_seed(2023 + rank)   # per-rank data / drop-path streams (main_pretrain.py:517)
     B = args.batch
@@ -614,7 +674,7 @@ def main():
     loss_and_grads = make_loss_and_grads(args.heads, [net.embed_dim] * 4 if hasattr(net, "embed_dim") else list(net.out_channels))      # (InternImage: 192 / 384 / 768 / 1536)
 
     timer = GemmTimer(ops)
-    if not args.no_gemm_timer:
+    if gemm_timer:
         timer.install()
 
     def sync():
@@ -625,7 +685,7 @@ def main():
     for _ in range(args.warmup):
         trainer.step(img, loss_and_grads)
     sync()
-    sampler = ClockSampler(torch.cuda.current_device()) if rank == 0 else None
+    sampler = ClockSampler(torch.cuda.current_device()) if (rank == 0 and args.full) else None
     if sampler is not None:
         sampler.start()
     t0 = time.perf_counter()
@@ -637,20 +697,24 @@ def main():
     eng_cls = type(trainer.engine)
     side_default = getattr(eng_cls, "wgrad_side_stream", False)
     conc_steps = 0
+    feat_samples = []          # --dump-outputs: the last timed step also samples its feature maps
+    last_lg = keep_feature_samples(loss_and_grads, feat_samples) if (args.dump_outputs and rank == 0) else loss_and_grads
     for i in range(args.steps):
-        timer.on = (not args.no_gemm_timer) and args.timer_every > 0 and i % args.timer_every == 0
+        timer.on = gemm_timer and args.timer_every > 0 and i % args.timer_every == 0
         if timer.on:
             timer.use(1 if side_default else 0)
             if side_default:
                 conc_steps += 1
             else:
                 timed_steps += 1
-        loss = trainer.step(img, loss_and_grads)
+        loss = trainer.step(img, last_lg if i == args.steps - 1 else loss_and_grads)
     sync()
     dt = time.perf_counter() - t0
     clocks = sampler.stop() if sampler is not None else None
     timer.on = False
-    if not args.no_gemm_timer:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, feat_samples, trainer.flat)
+    if gemm_timer:
         # the instrumented steps, right behind the timed region (same weights, same buffers, same clocks): first as the timed steps ran (`concurrent`,
         # engines with a weight-gradient side stream only), then with every launch on the one compute stream (`roofline` proper)
         n_inst = max(2, min(4, args.steps // 5))
@@ -680,7 +744,7 @@ def main():
     value = world * B * args.steps / dt
 
     comm = None
-    if trainer.reducer.active:
+    if args.full and trainer.reducer.active:
         # communication report (N > 1, or MTP_FORCE_COMM=1): the same steps once more with HIP events around every collective on the
         # side stream, and once with the collectives switched off -- the difference is what the overlap does not hide
         red = trainer.reducer
@@ -734,7 +798,7 @@ def main():
                          "backward); exposed = step time with minus without collectives; bus GB/s = bytes x 2(N-1)/N / all-reduce time")
 
     forward_only = None
-    if args.forward_only:
+    if args.full and args.forward_only:
         eng = trainer.engine
         for _ in range(args.warmup):
             eng.forward(img, training=False, need_grad=False, feature_dtype=fdt)
@@ -836,7 +900,7 @@ def main():
                                       " (BASELINE configs[4]'s backbone and tile size; stand-in loss instead of the segmentation decoder)" if args.model == "internimage_xl" and args.image_size == 512
                                       else (" (BASELINE configs[2]/[3])" if args.model == "vit_l" and B == 64 else " (BASELINE configs[1])" if args.model == "vit_b" and B == 32 else "")
                                       if args.image_size == 224 else " (not the headline configuration)"),
-                       "global_batch": world * B, "parallelism": "dp%d" % world, "loss": float(loss),
+                       "global_batch": world * B, "parallelism": "dp%d" % world, "loss": float(loss), "lr": args.lr,
                        "activation_checkpointing": bool(args.use_ckpt),
                        "heads": ("3 stand-in task heads (per-map 1x1 projection + mean each; the mm* decoders are not vendored)" if args.heads == "standin3"
                                  else "1 stand-in segmentation head (per-map 1x1 projection to 7 classes + per-pixel cross-entropy vs fixed random labels, torch autograd; "
@@ -855,7 +919,7 @@ def main():
             out["host_input"] = host_input
         if forward_only is not None:
             out["forward_only"] = forward_only
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.model)
     if dist.is_initialized():
         dist.destroy_process_group()

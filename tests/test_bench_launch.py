@@ -68,6 +68,38 @@ def test_world_size_mismatch_is_reported_as_json():
     assert out["value"] is None and "WORLD_SIZE" in out["error"]
 
 
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_alone_and_dumps_what_the_last_step_computed(tmp_path):
+    """a plain run prints the headline line and nothing that needs runs of its own; --full adds them; --dump-outputs writes the last timed
+    step's results as f32 / f64 .npy files under 64 MB, taken before --full's extra passes, from inputs that are the same in every run: at the
+    default learning rate 0 the weights keep their seeded values, and two runs agree up to the f32 atomics' reordered sums"""
+    import numpy as np
+    common = ["--gpus", "1", "--steps", "3", "--warmup", "2", "--model", "vit_b", "--batch", "4"]
+    rc, lines, err = _run(*common, "--dump-outputs", str(tmp_path / "plain"))
+    assert rc == 0, err[-2000:]
+    out = json.loads(lines[-1])
+    assert out["steps"] == 3 and out["warmup"] == 2 and out["value"] > 0 and out["ms_per_step"] > 0 and out["unit"] == "images/sec"
+    assert out["higher_is_better"] is True and out["dtype"] == "bf16" and out["metric"].startswith("images/sec")
+    assert out["roofline"] is None and not any(k in out for k in ("cpu_baseline", "forward_only", "clocks", "comm"))
+    rc, lines, err = _run(*common, "--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full"))
+    assert rc == 0, err[-2000:]
+    full = json.loads(lines[-1])
+    assert full["roofline"]["kernel"] in ("gemm_nt", "gemm_tn") and full["forward_only"]["value"] > 0 and "cpu_baseline" not in full
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names == sorted(os.listdir(tmp_path / "full")) == sorted(["loss.npy", "grads_sample.npy", "params_sample.npy"] + ["features_%d_sample.npy" % i for i in range(4)])
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "plain" / n), np.load(tmp_path / "full" / n)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape and np.isfinite(a).all()
+        total += a.nbytes
+        scale = max(float(np.abs(b).max()), 1e-30)
+        assert float(np.abs(a.astype(np.float64) - b).max()) / scale < 1e-5, n
+        if n == "params_sample.npy":
+            assert np.array_equal(a, b) and out["config"]["lr"] == 0.0
+    assert total <= 64 << 20
+    assert abs(float(np.load(tmp_path / "plain" / "loss.npy")[0]) - out["config"]["loss"]) <= 1e-6 * max(1.0, abs(out["config"]["loss"]))
+
+
 def test_traffic_is_quoted_only_for_matching_kernel_sources(tmp_path, monkeypatch):
     """roofline.traffic comes from the committed PMC passes -- and only while the hash of mtp_amd/csrc recorded in that file equals the tree's
     (VERDICT r02 #7): another hash -> None plus the reason in traffic_source"""

@@ -21,8 +21,8 @@ cp $(find $O/trace_single -name "t_kernel_stats.csv" | head -1) profiles/r06_roc
 python tools/hbm_fractions.py profiles/r06_rocprofv3_kernel_stats_single_stream.csv profiles/r06_pmc_hbm.json --json profiles/r06_hbm_fractions.json > profiles/r06_hbm_fractions.txt 2>> $O/pmc_hbm.err
 cp profiles/r06_pmc_hbm.json profiles/r06_rocprofv3_kernel_stats_single_stream.csv profiles/r06_hbm_fractions.json profiles/r06_hbm_fractions.txt $O/
 rm -rf $O/trace_single $O/pmc_fetch $O/pmc_write
-timeout -s KILL 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err
-timeout -s KILL 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-forward-only --gemm-shapes > /dev/null 2> $O/vitl_gemm_shapes.txt
+timeout -s KILL 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err
+timeout -s KILL 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-forward-only --gemm-shapes > /dev/null 2> $O/vitl_gemm_shapes.txt
 cd /tmp
 timeout -s KILL 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- python $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-gemm-timer --no-forward-only > $O/trace.log 2>&1
 cd $R
@@ -47,15 +47,15 @@ os.remove(f)
 PY
 cp $(find $O/trace -name "t_kernel_stats.csv" | head -1) $O/kernel_stats.csv
 rm -rf $O/trace
-MTP_RCCL_LOG_COPY=$O/rccl_rank0.log MTP_FORCE_COMM=1 timeout -s KILL 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-forward-only > $O/bench_n1_forced_comm.json 2>> $O/bench_n1.err
-MTP_FORCE_COMM=1 timeout -s KILL 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-forward-only --comm-mode rs_ag --comm-bf16 > $O/bench_n1_forced_comm_rs_ag_bf16.json 2>> $O/bench_n1.err
+MTP_RCCL_LOG_COPY=$O/rccl_rank0.log MTP_FORCE_COMM=1 timeout -s KILL 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-forward-only > $O/bench_n1_forced_comm.json 2>> $O/bench_n1.err
+MTP_FORCE_COMM=1 timeout -s KILL 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-forward-only --comm-mode rs_ag --comm-bf16 > $O/bench_n1_forced_comm_rs_ag_bf16.json 2>> $O/bench_n1.err
 rm -f $O/rccl_rank0.log
-timeout -s KILL 300 python bench.py --model vit_b --batch 32 --heads standin3 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_config2_vitb_b32_standin3.json 2>> $O/bench_n1.err
-timeout -s KILL 300 python bench.py --image-size 448 --batch 16 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_vitl_448_b16.json 2>> $O/bench_n1.err
-timeout -s KILL 300 python bench.py --image-size 448 --batch 16 --use-ckpt --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_vitl_448_b16_ckpt.json 2>> $O/bench_n1.err
-timeout -s KILL 300 python bench.py --model internimage_xl --image-size 512 --batch 8 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_internimage_xl_512_b8.json 2>> $O/bench_n1.err
-timeout -s KILL 300 python bench.py --model internimage_xl --image-size 512 --batch 8 --use-ckpt --steps 10 --warmup 3 --no-cpu-baseline --no-forward-only > $O/bench_internimage_xl_512_b8_with_cp.json 2>> $O/bench_n1.err
-timeout -s KILL 300 python bench.py --model internimage_xl --image-size 512 --batch 8 --heads standin_seg --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_internimage_xl_512_b8_standin_seg.json 2>> $O/bench_n1.err
+timeout -s KILL 300 python bench.py --full --model vit_b --batch 32 --heads standin3 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_config2_vitb_b32_standin3.json 2>> $O/bench_n1.err
+timeout -s KILL 300 python bench.py --full --image-size 448 --batch 16 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_vitl_448_b16.json 2>> $O/bench_n1.err
+timeout -s KILL 300 python bench.py --full --image-size 448 --batch 16 --use-ckpt --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_vitl_448_b16_ckpt.json 2>> $O/bench_n1.err
+timeout -s KILL 300 python bench.py --full --model internimage_xl --image-size 512 --batch 8 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_internimage_xl_512_b8.json 2>> $O/bench_n1.err
+timeout -s KILL 300 python bench.py --full --model internimage_xl --image-size 512 --batch 8 --use-ckpt --steps 10 --warmup 3 --no-cpu-baseline --no-forward-only > $O/bench_internimage_xl_512_b8_with_cp.json 2>> $O/bench_n1.err
+timeout -s KILL 300 python bench.py --full --model internimage_xl --image-size 512 --batch 8 --heads standin_seg --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_internimage_xl_512_b8_standin_seg.json 2>> $O/bench_n1.err
 cd /tmp
 timeout -s KILL 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_intern1 -o t -- python $R/bench.py --model internimage_xl --image-size 512 --batch 8 --steps 4 --warmup 2 --no-cpu-baseline --no-gemm-timer --no-forward-only --wgrad-side-stream 0 > $O/trace_intern1.log 2>&1
 timeout -s KILL 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_vitb -o t -- python $R/bench.py --model vit_b --batch 32 --heads standin3 --steps 6 --warmup 2 --no-cpu-baseline --no-gemm-timer --no-forward-only --wgrad-side-stream 0 > $O/trace_vitb.log 2>&1
@@ -63,16 +63,16 @@ cd $R
 cp $(find $O/trace_intern1 -name "t_kernel_stats.csv" | head -1) $O/internimage_xl_kernel_stats_single_stream.csv
 cp $(find $O/trace_vitb -name "t_kernel_stats.csv" | head -1) $O/vitb_b32_standin3_kernel_stats_single_stream.csv
 rm -rf $O/trace_intern1 $O/trace_vitb
-timeout -s KILL 400 python bench.py --steps 200 --warmup 5 --no-cpu-baseline --no-forward-only > $O/bench_n1_200steps.json 2>> $O/bench_n1.err
+timeout -s KILL 400 python bench.py --full --steps 200 --warmup 5 --no-cpu-baseline --no-forward-only > $O/bench_n1_200steps.json 2>> $O/bench_n1.err
 for i in 1 2 3; do
   (cd $R/_base && timeout -s KILL 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-forward-only > $O/ab_base_$i.json 2>> $O/ab.err)
-  timeout -s KILL 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-forward-only > $O/ab_new_$i.json 2>> $O/ab.err
+  timeout -s KILL 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-forward-only > $O/ab_new_$i.json 2>> $O/ab.err
 done
 for i in 1 2; do
   (cd $R/_base && timeout -s KILL 300 python bench.py --model vit_b --batch 32 --heads standin3 --steps 20 --warmup 5 --no-cpu-baseline --no-forward-only > $O/vitb_base_$i.json 2>> $O/ab.err)
-  timeout -s KILL 300 python bench.py --model vit_b --batch 32 --heads standin3 --steps 20 --warmup 5 --no-cpu-baseline --no-forward-only > $O/vitb_new_$i.json 2>> $O/ab.err
+  timeout -s KILL 300 python bench.py --full --model vit_b --batch 32 --heads standin3 --steps 20 --warmup 5 --no-cpu-baseline --no-forward-only > $O/vitb_new_$i.json 2>> $O/ab.err
   (cd $R/_base && timeout -s KILL 300 python bench.py --model internimage_xl --image-size 512 --batch 8 --steps 10 --warmup 3 --no-cpu-baseline --no-forward-only > $O/ii_base_$i.json 2>> $O/ab.err)
-  timeout -s KILL 300 python bench.py --model internimage_xl --image-size 512 --batch 8 --steps 10 --warmup 3 --no-cpu-baseline --no-forward-only > $O/ii_new_$i.json 2>> $O/ab.err
+  timeout -s KILL 300 python bench.py --full --model internimage_xl --image-size 512 --batch 8 --steps 10 --warmup 3 --no-cpu-baseline --no-forward-only > $O/ii_new_$i.json 2>> $O/ab.err
 done
 python - <<PY > $O/ab_vs_round5.txt
 import json, glob
