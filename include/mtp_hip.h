@@ -199,6 +199,10 @@ int mtp_weight_images(const mtp_wimg_desc* descs_dev, int n, int64_t total_tiles
  * NULL: parameters that no GEMM reads).  Descriptors must cover every parameter that is to be updated exactly once. */
 int mtp_adamw_weight_images(const mtp_wimg_desc* descs_dev, int n, int64_t total_tiles, int act_dtype, float* p_base, const float* g_base, float* m_base, float* v_base,
                             const float* hyper, const float* sqnorm, float max_norm, float grad_scale, mtp_stream_t stream);
+/* The same with layer-wise lr decay: descriptor d is updated with lr = hyper[0] * desc_lr[d] (device f32[n], the group's lr_scale) in the decay factor 1 - lr * wd
+ * and the step lr / bias_corr1 -- torch.optim.AdamW with a per-group lr.  desc_lr is a table of its own: mtp_wimg_desc is unchanged. */
+int mtp_adamw_weight_images_lr(const mtp_wimg_desc* descs_dev, const float* desc_lr, int n, int64_t total_tiles, int act_dtype, float* p_base, const float* g_base,
+                               float* m_base, float* v_base, const float* hyper, const float* sqnorm, float max_norm, float grad_scale, mtp_stream_t stream);
 /* ConvTranspose2d weight (Cin, Cout, 2, 2) f32 -> GEMM weight wg (4*Cout, Cin) and its transpose wgT (Cin, 4*Cout) */
 int mtp_convt_pack(const float* w, void* wg, void* wgT, int dtype, int64_t Cin, int64_t Cout, mtp_stream_t stream);
 /* dwg (4*Cout, Cin) f32 -> dw (Cin, Cout, 2, 2) f32 */
@@ -333,6 +337,9 @@ int mtp_sqnorm_segments_f32(const float* base, const int64_t* start, const int64
  * hyper (device, f32[6]) = {lr, beta1, beta2, eps, bias_corr1, bias_corr2}; clip_coef = min(1, max_norm / (sqrt(*sqnorm)+1e-6)) if sqnorm */
 int mtp_adamw_flat(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_start, const float* seg_wd, int nseg,
                    const float* hyper, const float* sqnorm, float max_norm, float grad_scale, mtp_stream_t stream);
+/* The same with layer-wise lr decay: segment s is updated with lr = hyper[0] * seg_lr[s] (device f32[nseg], the group's lr_scale) */
+int mtp_adamw_flat_lr(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_start, const float* seg_wd, const float* seg_lr, int nseg,
+                      const float* hyper, const float* sqnorm, float max_norm, float grad_scale, mtp_stream_t stream);
 
 /* ---- DCNv3 core (InternImage) ------------------------------------------------------------------------
  * The reference's own native extension: `dcnv3_forward(input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h,

@@ -124,6 +124,8 @@ SIGNATURES = {
     "mtp_sqnorm_segments_f32": (i32, [p, p, p, i32, p, p]),
     "mtp_adamw_flat": (i32, [p, p, p, p, i64, p, p, i32, p, p, f32, f32, p]),
     "mtp_adamw_weight_images": (i32, [p, i32, i64, i32, p, p, p, p, p, p, f32, f32, p]),
+    "mtp_adamw_flat_lr": (i32, [p, p, p, p, i64, p, p, p, i32, p, p, f32, f32, p]),
+    "mtp_adamw_weight_images_lr": (i32, [p, p, i32, i64, i32, p, p, p, p, p, p, f32, f32, p]),
     "mtp_version": (C.c_char_p, []),
     "mtp_stream_create_low_priority": (i32, [p]),
     "mtp_stream_create_cu_mask": (i32, [p, i32, p]),

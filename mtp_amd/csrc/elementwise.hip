@@ -614,17 +614,20 @@ __global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ g
 
 // AdamW (torch.optim.AdamW semantics, MAIN:424-457) over a flat buffer; segments start at multiples of 4 elements.
 // (round 5: nontemporal loads / stores on all seven streams: 1660 -> 1603 us alone, no difference in the step -- profiles/r05_ab_late_adamw_nontemporal.txt; not kept)
+// kLr: layer-wise lr decay -- segment s trains at lr = hyper[0] * seg_lr[s] (torch.optim.AdamW with a per-group lr); without it the
+// code is the plain one (no seg_lr load, no multiply).
+template <bool kLr>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
-                                                   const int64_t* __restrict__ seg_start, const float* __restrict__ seg_wd, int nseg,
+                                                   const int64_t* __restrict__ seg_start, const float* __restrict__ seg_wd, const float* __restrict__ seg_lr, int nseg,
                                                    const float* __restrict__ hyper, const float* __restrict__ sqnorm, float max_norm, float grad_scale) {
-    const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], bc1 = hyper[4], bc2 = hyper[5];
+    const float lr0 = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], bc1 = hyper[4], bc2 = hyper[5];
     float gs = grad_scale;
     if (sqnorm) {
         const float total = sqrtf(*sqnorm) * grad_scale;
         const float coef = max_norm / (total + 1e-6f);
         gs *= coef < 1.0f ? coef : 1.0f;
     }
-    const float rbc2 = rsqrtf(bc2), step = lr / bc1;
+    const float rbc2 = rsqrtf(bc2), step0 = lr0 / bc1;
     const int64_t n4 = n >> 2;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         int lo = 0, hi = nseg - 1;   // last segment with start <= 4*i
@@ -632,6 +635,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
             const int mid = (lo + hi + 1) >> 1;
             if (seg_start[mid] <= 4 * i) lo = mid; else hi = mid - 1;
         }
+        const float lr = kLr ? lr0 * seg_lr[lo] : lr0, step = kLr ? lr / bc1 : step0;
         const float decay = 1.0f - lr * seg_wd[lo];
         float4 pv = load4(p + 4 * i), gv = load4(g + 4 * i), mv = load4(m + 4 * i), vv = load4(v + 4 * i);
         float P[4] = {pv.x, pv.y, pv.z, pv.w}, G[4] = {gv.x, gv.y, gv.z, gv.w}, M[4] = {mv.x, mv.y, mv.z, mv.w}, V[4] = {vv.x, vv.y, vv.z, vv.w};
@@ -850,9 +854,10 @@ __device__ __forceinline__ void adamw_elem(float& P, float G, float& M, float& V
     P -= step * M / (sqrtf(V) * rbc2 + eps);
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void adamw_images_kernel(const mtp_wimg_desc* __restrict__ descs, int n, const float* __restrict__ p_base, const float* __restrict__ g_base,
-                                                          float* __restrict__ m_base, float* __restrict__ v_base, const float* __restrict__ hyper,
+// kLr: layer-wise lr decay -- descriptor d trains at lr = hyper[0] * desc_lr[d] (one scalar load per workgroup; a table of its own, so mtp_wimg_desc keeps its layout)
+template <typename T, bool kLr>
+__global__ __launch_bounds__(256) void adamw_images_kernel(const mtp_wimg_desc* __restrict__ descs, const float* __restrict__ desc_lr, int n, const float* __restrict__ p_base,
+                                                          const float* __restrict__ g_base, float* __restrict__ m_base, float* __restrict__ v_base, const float* __restrict__ hyper,
                                                           const float* __restrict__ sqnorm, float max_norm, float grad_scale) {
     __shared__ float tile[64][65];
     const int64_t tl = blockIdx.x;
@@ -862,7 +867,7 @@ __global__ __launch_bounds__(256) void adamw_images_kernel(const mtp_wimg_desc* 
         if (descs[mid].tile0 <= tl) lo = mid; else hi = mid - 1;
     }
     const mtp_wimg_desc d = descs[lo];
-    const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], bc1 = hyper[4], bc2 = hyper[5];
+    const float lr = kLr ? hyper[0] * desc_lr[lo] : hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], bc1 = hyper[4], bc2 = hyper[5];
     float gs = grad_scale;
     if (sqnorm) {
         const float total = sqrtf(*sqnorm) * grad_scale;
@@ -970,12 +975,27 @@ __global__ __launch_bounds__(256) void adamw_images_kernel(const mtp_wimg_desc* 
 extern "C" int mtp_adamw_weight_images(const mtp_wimg_desc* descs_dev, int n, int64_t total_tiles, int act_dtype, float* p_base, const float* g_base, float* m_base,
                                        float* v_base, const float* hyper, const float* sqnorm, float max_norm, float grad_scale, mtp_stream_t stream) {
     if (!descs_dev || n <= 0 || total_tiles <= 0 || total_tiles > INT32_MAX || !p_base || !g_base || !m_base || !v_base || !hyper) return MTP_ERR_ARG;
+    const float* no_lr = nullptr;
     if (act_dtype == MTP_BF16)
-        hipLaunchKernelGGL((adamw_images_kernel<bf16_t>), dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, descs_dev, n, p_base, g_base, m_base, v_base, hyper,
-                           sqnorm, max_norm, grad_scale);
+        hipLaunchKernelGGL((adamw_images_kernel<bf16_t, false>), dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, descs_dev, no_lr, n, p_base, g_base, m_base,
+                           v_base, hyper, sqnorm, max_norm, grad_scale);
     else if (act_dtype == MTP_F32)
-        hipLaunchKernelGGL((adamw_images_kernel<float>), dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, descs_dev, n, p_base, g_base, m_base, v_base, hyper,
-                           sqnorm, max_norm, grad_scale);
+        hipLaunchKernelGGL((adamw_images_kernel<float, false>), dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, descs_dev, no_lr, n, p_base, g_base, m_base,
+                           v_base, hyper, sqnorm, max_norm, grad_scale);
+    else return MTP_ERR_UNSUPPORTED;
+    return mtp_launch_status();
+}
+
+extern "C" int mtp_adamw_weight_images_lr(const mtp_wimg_desc* descs_dev, const float* desc_lr, int n, int64_t total_tiles, int act_dtype, float* p_base,
+                                          const float* g_base, float* m_base, float* v_base, const float* hyper, const float* sqnorm, float max_norm, float grad_scale,
+                                          mtp_stream_t stream) {
+    if (!descs_dev || !desc_lr || n <= 0 || total_tiles <= 0 || total_tiles > INT32_MAX || !p_base || !g_base || !m_base || !v_base || !hyper) return MTP_ERR_ARG;
+    if (act_dtype == MTP_BF16)
+        hipLaunchKernelGGL((adamw_images_kernel<bf16_t, true>), dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, descs_dev, desc_lr, n, p_base, g_base, m_base,
+                           v_base, hyper, sqnorm, max_norm, grad_scale);
+    else if (act_dtype == MTP_F32)
+        hipLaunchKernelGGL((adamw_images_kernel<float, true>), dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, descs_dev, desc_lr, n, p_base, g_base, m_base,
+                           v_base, hyper, sqnorm, max_norm, grad_scale);
     else return MTP_ERR_UNSUPPORTED;
     return mtp_launch_status();
 }
@@ -1441,7 +1461,16 @@ extern "C" int mtp_sqnorm_f32(const float* g, float* out, int64_t n, mtp_stream_
 extern "C" int mtp_adamw_flat(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_start, const float* seg_wd, int nseg,
                               const float* hyper, const float* sqnorm, float max_norm, float grad_scale, mtp_stream_t stream) {
     if (!p || !g || !m || !v || n <= 0 || (n % 4) || !seg_start || !seg_wd || nseg <= 0 || !hyper) return MTP_ERR_ARG;
-    hipLaunchKernelGGL(adamw_kernel, dim3(blocks_for(n / 4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, seg_start, seg_wd, nseg, hyper, sqnorm, max_norm, grad_scale);
+    hipLaunchKernelGGL(adamw_kernel<false>, dim3(blocks_for(n / 4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, seg_start, seg_wd,
+                       (const float*)nullptr, nseg, hyper, sqnorm, max_norm, grad_scale);
+    return mtp_launch_status();
+}
+
+extern "C" int mtp_adamw_flat_lr(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_start, const float* seg_wd, const float* seg_lr,
+                                 int nseg, const float* hyper, const float* sqnorm, float max_norm, float grad_scale, mtp_stream_t stream) {
+    if (!p || !g || !m || !v || n <= 0 || (n % 4) || !seg_start || !seg_wd || !seg_lr || nseg <= 0 || !hyper) return MTP_ERR_ARG;
+    hipLaunchKernelGGL(adamw_kernel<true>, dim3(blocks_for(n / 4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, seg_start, seg_wd, seg_lr, nseg,
+                       hyper, sqnorm, max_norm, grad_scale);
     return mtp_launch_status();
 }
 
@@ -1474,7 +1503,8 @@ extern "C" int mtp_scale_rows_cast(const float* src, void* dst, int dst_dtype, c
 // mtp_gemm_tn_grouped honours split_k / aux.  Bump whenever a struct in include/mtp_hip.h changes size or a field changes meaning.
 // 0.5: round 5 -- no struct changed; mtp_gemm_args.variant gained bits 17 / 18 (strip kernel) and 19 (grouped TN: plain phases), mtp_gemm_nt_tile may answer 64.
 // 0.6: round 6 -- mtp_wimg_desc.pad_ became `float wd` (same size; read only by mtp_adamw_weight_images); new entry points mtp_adamw_weight_images, mtp_stream_create_cu_mask,
-// mtp_probe_placement, mtp_comm_info.
+// mtp_probe_placement, mtp_comm_info.  Later additions, no struct changed: mtp_adamw_flat_lr / mtp_adamw_weight_images_lr (layer-wise lr decay: a per-segment /
+// per-descriptor lr scale in a device table of its own).
 extern "C" const char* mtp_version(void) { return "mtp_hip 0.6 (gfx950)"; }
 
 // A stream of the LOWEST priority the device offers (non-blocking), for work that is off the critical path and should only take the CUs

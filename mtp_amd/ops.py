@@ -533,12 +533,13 @@ class AdamWImages:
     None is returned by build() when an image source is not a whole flat parameter (layer scale: the images are made from scaled temporaries)."""
 
     @staticmethod
-    def build(flat, wimg, wd_of):
+    def build(flat, wimg, wd_of, lr_of=None):
+        """lr_of(name) -> lr scale (layer-wise lr decay): step() then runs mtp_adamw_weight_images_lr with a per-descriptor scale table.  None: the plain entry point."""
         by_ptr = {}
         for src, w, wt, f32_out in (wimg.entries if wimg is not None else []):
             by_ptr[src.data_ptr()] = (src, w, wt, f32_out)
         base = flat.data.data_ptr()
-        rows = []
+        rows, scales = [], []
         used = 0
         for n in flat.names:
             if flat.groups[n] is None:
@@ -560,6 +561,7 @@ class AdamWImages:
                 padded = (numel + 63) // 64 * 64          # FlatParams pads every parameter to 64 elements: the tail is zero and stays zero
                 R, Cc = padded // 64, 64
             rows.append((base + 4 * off, w, wt, R, Cc, f32_out, float(wd_of(n))))
+            scales.append(1.0 if lr_of is None else float(lr_of(n)))
         if used != len(by_ptr):
             return None               # an image whose source is not a flat parameter
         self = AdamWImages()
@@ -575,11 +577,16 @@ class AdamWImages:
         self.n, self.total_tiles = len(rows), tile0
         self.act = _DT[wimg.act_dtype] if wimg is not None else MTP_BF16
         self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(flat.data.device)
+        self.lr = None if lr_of is None else torch.tensor(scales, dtype=torch.float32).to(flat.data.device)     # (one scale per descriptor)
         self.flat = flat
         return self
 
     def step(self, m, v, hyper, sqn, max_norm, grad_scale):
         f = self.flat
+        if self.lr is not None:
+            check(lib().mtp_adamw_weight_images_lr(self.table.data_ptr(), _f32(self.lr), self.n, self.total_tiles, self.act, _f32(f.data), _f32(f.grad), _f32(m), _f32(v),
+                                                   _f32(hyper), _f32(sqn), max_norm, grad_scale, _s()), "mtp_adamw_weight_images_lr")
+            return
         check(lib().mtp_adamw_weight_images(self.table.data_ptr(), self.n, self.total_tiles, self.act, _f32(f.data), _f32(f.grad), _f32(m), _f32(v), _f32(hyper),
                                             _f32(sqn), max_norm, grad_scale, _s()), "mtp_adamw_weight_images")
 
@@ -784,6 +791,13 @@ def adamw_flat(p, g, m, v, seg_start, seg_wd, hyper, sqn=None, max_norm=0.0, gra
     assert seg_start.dtype == torch.int64 and seg_start.is_cuda
     check(lib().mtp_adamw_flat(_f32(p), _f32(g), _f32(m), _f32(v), p.numel(), seg_start.data_ptr(), _f32(seg_wd), seg_start.numel(),
                                _f32(hyper), _f32(sqn), max_norm, grad_scale, _s()), "mtp_adamw_flat")
+
+
+def adamw_flat_lr(p, g, m, v, seg_start, seg_wd, seg_lr, hyper, sqn=None, max_norm=0.0, grad_scale=1.0):
+    """adamw_flat with layer-wise lr decay: segment s trains at lr = hyper[0] * seg_lr[s]"""
+    assert seg_start.dtype == torch.int64 and seg_start.is_cuda and seg_lr.numel() == seg_start.numel() == seg_wd.numel()
+    check(lib().mtp_adamw_flat_lr(_f32(p), _f32(g), _f32(m), _f32(v), p.numel(), seg_start.data_ptr(), _f32(seg_wd), _f32(seg_lr), seg_start.numel(),
+                                  _f32(hyper), _f32(sqn), max_norm, grad_scale, _s()), "mtp_adamw_flat_lr")
 
 
 # ------------------------------------------------------------------------------------------------ InternImage layers (csrc/conv.hip)

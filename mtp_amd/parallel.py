@@ -138,6 +138,27 @@ class FlatParams:
             wds.append(0.0 if nd else weight_decay)
         return torch.tensor(starts, dtype=torch.int64), torch.tensor(wds, dtype=torch.float32)
 
+    def group_segments(self, param_groups):
+        """per-parameter segments (start offsets, wd, lr scale) from [(group_name, lr_scale, weight_decay, [names])].  Every parameter that
+        receives a gradient must be in exactly one group; the others (outside the updated range) get wd 0, scale 1."""
+        of = {}
+        for g, scale, wd, names in param_groups:
+            for n in names:
+                if n in of:
+                    raise ValueError("parameter %r is in two optimizer groups (%s, %s)" % (n, of[n][0], g))
+                of[n] = (g, scale, wd)
+        missing = [n for n in self.names if self.groups[n] is not None and n not in of]
+        if missing:
+            raise ValueError("%d trained parameters are in no optimizer group (first: %r); a parameter with requires_grad=False inside the trained range "
+                             "is not supported with layer-wise lr decay" % (len(missing), missing[0]))
+        starts, wds, lrs = [], [], []
+        for n in self.names:
+            _, scale, wd = of.get(n, (None, 1.0, 0.0))
+            starts.append(self.offsets[n])
+            wds.append(wd)
+            lrs.append(scale)
+        return torch.tensor(starts, dtype=torch.int64), torch.tensor(wds, dtype=torch.float32), torch.tensor(lrs, dtype=torch.float32)
+
 
 def reference_param_groups(named_params, weight_decay, prefix="encoder."):
     """Parameter groups as LayerDecayOptimizerConstructor_ViT.add_params builds them
@@ -366,14 +387,23 @@ class FlatAdamW:
     """torch.optim.AdamW semantics over FlatParams (lr 6e-5, betas (0.9, 0.999), wd 0.05 in the reference) with the
     cosine schedule of main_pretrain.py:832 and clip_grad_norm_(max_norm=5) of main_pretrain.py:786."""
 
-    def __init__(self, flat, lr=6e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05, max_norm=5.0, total_steps=None, world_size=1):
+    def __init__(self, flat, lr=6e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05, max_norm=5.0, total_steps=None, world_size=1, param_groups=None):
+        """param_groups: [(group_name, lr_scale, weight_decay, [names])] (mtp_amd.optim_groups.layer_decay_param_groups) -- every trained parameter
+        takes its group's lr scale and weight decay (torch.optim.AdamW with per-group lr; the *_lr kernels).  None: reference_param_groups' two
+        groups, lr_scale 1 and the no-decay rule of FlatParams.weight_decay_segments."""
         self.flat, self.lr0, self.betas, self.eps, self.max_norm = flat, lr, betas, eps, max_norm
         self.weight_decay = weight_decay
         self.total_steps, self.world = total_steps, world_size
         dev = flat.data.device
         self.m = torch.zeros_like(flat.data)
         self.v = torch.zeros_like(flat.data)
-        st, wd = flat.weight_decay_segments(weight_decay)
+        self.param_groups, self.seg_lr = None, None
+        if param_groups is None:
+            st, wd = flat.weight_decay_segments(weight_decay)
+        else:
+            self.param_groups = [(g, float(s), float(w), list(ns)) for g, s, w, ns in param_groups]
+            st, wd, lr = flat.group_segments(self.param_groups)
+            self.seg_lr = lr.to(dev)
         self.seg_start, self.seg_wd = st.to(dev), wd.to(dev)
         self.hyper = torch.zeros(6, device=dev, dtype=torch.float32)
         self.sqn = torch.zeros(1, device=dev, dtype=torch.float32)
@@ -394,12 +424,18 @@ class FlatAdamW:
         return [self.lr_at(self.last_epoch), b1, b2, self.eps, 1.0 - b1 ** self.t, 1.0 - b2 ** self.t]
 
     # ---- checkpoint / resume in the reference's formats (MAIN:483-499, 823-829) --------------------------------------------
+    def groups_for(self, module):
+        """the optimizer's parameter groups: the layer-decay groups it was built with, else the two the reference builds for an encoder.* backbone"""
+        if self.param_groups is not None:
+            return self.param_groups
+        return reference_param_groups(module.named_parameters(), self.weight_decay)
+
     def state_dict(self, module):
         """torch.optim.AdamW.state_dict() layout for the parameter groups the reference builds (reference_param_groups):
         loadable by a torch AdamW constructed the same way and vice versa.  Parameters that never receive a gradient
         (`norm.*`) carry no state, as in torch."""
         f = self.flat
-        groups = reference_param_groups(module.named_parameters(), self.weight_decay)
+        groups = self.groups_for(module)
         state, pgs, idx = {}, [], 0
         for name, scale, wd, names in groups:
             ids = []
@@ -422,7 +458,7 @@ class FlatAdamW:
         own older files, plain torch) fall back to positional matching, which needs the same parameter list.
         Returns the number of parameters restored."""
         f = self.flat
-        own = [n for g in reference_param_groups(module.named_parameters(), self.weight_decay) for n in g[3]]
+        own = [n for g in self.groups_for(module) for n in g[3]]
         pairs = []      # (optimizer state index, our parameter name)
         named = all("param_names" in pg and len(pg["param_names"]) == len(pg["params"]) for pg in sd["param_groups"])
         if named:
@@ -458,6 +494,10 @@ class FlatAdamW:
 
     def scheduler_state_dict(self):
         """the fields of torch.optim.lr_scheduler.CosineAnnealingLR.state_dict() (MAIN:457: T_max = end_iter, eta_min = 0)"""
+        if self.param_groups is not None:        # one base lr per group: lr0 * lr_scale
+            scales = [s for _, s, _, _ in self.param_groups]
+            return {"T_max": self.total_steps, "eta_min": 0, "base_lrs": [self.lr0 * s for s in scales], "last_epoch": self.last_epoch, "verbose": False,
+                    "_step_count": self.last_epoch + 1, "_get_lr_called_within_step": False, "_last_lr": [self.lr_at(self.last_epoch) * s for s in scales]}
         return {"T_max": self.total_steps, "eta_min": 0, "base_lrs": [self.lr0, self.lr0], "last_epoch": self.last_epoch, "verbose": False,
                 "_step_count": self.last_epoch + 1, "_get_lr_called_within_step": False, "_last_lr": [self.lr_at(self.last_epoch)] * 2}
 
@@ -479,6 +519,10 @@ class FlatAdamW:
         self._fused, self._fused_for = None, wimg
         if wimg is None or not self.flat.data.is_cuda or os.environ.get("MTP_FUSED_ADAMW", "1") == "0":
             return False
+        if self.param_groups is not None:        # layer-wise lr decay: the group's weight decay and lr scale (= FlatParams.group_segments)
+            of = {n: (s, w) for _, s, w, ns in self.param_groups for n in ns}
+            self._fused = ops.AdamWImages.build(self.flat, wimg, lambda n: of[n][1], lr_of=lambda n: of[n][0])
+            return self._fused is not None
         no_decay = ("pos_embed", "cls_token")
         wd = lambda n: 0.0 if (len(self.flat.shapes[n]) == 1 or n.endswith(".bias") or n in no_decay) else self.weight_decay      # (= FlatParams.weight_decay_segments)
         self._fused = ops.AdamWImages.build(self.flat, wimg, wd)
@@ -535,6 +579,9 @@ class FlatAdamW:
         if getattr(self, "_fused", None) is not None:
             self._fused.step(self.m, self.v, self.hyper, sq, float(self.max_norm or 0.0), gs)
             return True
+        if self.seg_lr is not None:
+            ops.adamw_flat_lr(f.data[:n], f.grad[:n], self.m[:n], self.v[:n], self.seg_start, self.seg_wd, self.seg_lr, self.hyper, sq, float(self.max_norm or 0.0), gs)
+            return False
         ops.adamw_flat(f.data[:n], f.grad[:n], self.m[:n], self.v[:n], self.seg_start, self.seg_wd, self.hyper, sq, float(self.max_norm or 0.0), gs)
         return False
 
@@ -543,15 +590,28 @@ class DataParallelTrainer:
     """fwd -> loss -> bwd (+ overlapped bucketed all-reduce) -> clip + AdamW, on the HIP engine."""
 
     def __init__(self, module, lr=6e-5, weight_decay=0.05, max_norm=5.0, total_steps=None, bucket_bytes=64 << 20, feature_dtype=None,
-                 comm_mode=None, comm_bf16=None):
+                 comm_mode=None, comm_bf16=None, optim_wrapper=None, param_prefix="encoder."):
+        """optim_wrapper: the reference's mmengine-style dict (e.g. mtp_amd.optim_groups.pretrain_optim_wrapper('vit_l')) -- its lr, betas and weight decay
+        replace the keywords, and its constructor's layer-wise lr decay groups are built with the parameter names prefixed by `param_prefix`
+        ('encoder.' as in the pretraining script, 'backbone.' as in the fine-tune frameworks).  None: the reference_param_groups optimizer."""
         self.module = module
+        betas, groups = (0.9, 0.999), None
+        if optim_wrapper is not None:
+            from .optim_groups import layer_decay_param_groups, optimizer_hyper
+            frozen = [n for n, p in module.named_parameters() if not p.requires_grad and n not in module._unused_params]
+            if frozen:
+                raise ValueError("layer-wise lr decay with frozen parameters is not supported: %d parameters inside the trained range have requires_grad=False "
+                                 "(first: %r)" % (len(frozen), frozen[0]))
+            lr, betas, weight_decay = optimizer_hyper(optim_wrapper)
+            groups = layer_decay_param_groups(module.named_parameters(), optim_wrapper, prefix=param_prefix)
         self.engine = module._engine()
         self.flat = FlatParams(module, unused=module._unused_params)
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         if self.flat.data.is_cuda and hasattr(self.engine, "warm_streams"):
             self.engine.warm_streams(self.flat.data.device)      # before the reducer creates its RCCL communicator
         self.reducer = GradReducer(self.flat, bucket_bytes, mode=comm_mode, bf16=comm_bf16)
-        self.opt = FlatAdamW(self.flat, lr=lr, weight_decay=weight_decay, max_norm=max_norm, total_steps=total_steps, world_size=self.world)
+        self.opt = FlatAdamW(self.flat, lr=lr, betas=betas, weight_decay=weight_decay, max_norm=max_norm, total_steps=total_steps, world_size=self.world,
+                             param_groups=groups)
         self.feature_dtype = feature_dtype
         self.sync_replicas()
 
