@@ -422,6 +422,51 @@ int mtp_comm_allgather_bucket(void* comm, void* bucket, int64_t count_per_rank, 
 int mtp_comm_info(void* comm, int* info4);
 int mtp_comm_destroy(void* comm);
 
+/* ---- UperNet decode head (mmseg UPerHead; csrc/decode_head.hip) ------------------------------------------------------
+ * Channels-last maps (rows = N*H*W, C) with row pitches ld (elements, multiples of 4); C a multiple of 4.  Statistics f32; every reduction is
+ * deterministic (fixed-order partial rows, no float atomics).
+ * BatchNorm (+ ReLU), training:  mtp_bn_stats -> sums (2C) f32 = [sum (x - center) | sum (x - center)^2] (center (C) f32 or NULL = 0), summed in
+ *   a fixed order from per-workgroup partial rows (workspace part: mtp_bn_partial_rows(rows) x 2C f32); [SyncBN: the host all-reduces sums here];
+ *   mtp_bn_finalize(sums, center, count, ...) -> mean / rstd (C), running stats updated (momentum, unbiased variance; NULL = not tracked).  Two
+ *   passes keep the variance exact when |mean| >> std: stats + finalize without center give a first mean, stats + finalize centred on it the result;
+ *   mtp_bn_finalize(NULL, NULL, 0, running_mean, running_var, ...) gives the eval statistics;  mtp_bn_apply -> y = relu?(gamma (x - mean) rstd + beta).
+ * Backward: mtp_bn_bwd_stats -> sums (2C) = [sum dy' | sum dy' xhat] (dy' = dy masked by the ReLU, recomputed from x), same workspace [SyncBN:
+ *   all-reduce]; those sums are d beta / d gamma of this rank;  mtp_bn_bwd_dx(sums, count) -> dx (sums NULL: eval statistics, dx = gamma rstd dy'). */
+int64_t mtp_bn_partial_rows(int64_t rows);
+int mtp_bn_stats(const void* x, int dtype, int64_t ldx, const float* center, float* part, float* sums, int64_t rows, int64_t C, mtp_stream_t stream);
+int mtp_bn_finalize(const float* sums, const float* center, double count, float* running_mean, float* running_var, float momentum, float eps, float* mean, float* rstd,
+                    int64_t C, mtp_stream_t stream);
+int mtp_bn_apply(const void* x, int x_dtype, int64_t ldx, const float* mean, const float* rstd, const float* gamma, const float* beta, int relu,
+                 void* y, int y_dtype, int64_t ldy, int64_t rows, int64_t C, mtp_stream_t stream);
+int mtp_bn_bwd_stats(const void* dy, int dy_dtype, int64_t lddy, const void* x, int x_dtype, int64_t ldx, const float* mean, const float* rstd,
+                     const float* gamma, const float* beta, int relu, float* part, float* sums, int64_t rows, int64_t C, mtp_stream_t stream);
+int mtp_bn_bwd_dx(const void* dy, int dy_dtype, int64_t lddy, const void* x, int x_dtype, int64_t ldx, const float* mean, const float* rstd,
+                  const float* gamma, const float* beta, int relu, const float* sums, double count, void* dx, int dx_dtype, int64_t lddx,
+                  int64_t rows, int64_t C, mtp_stream_t stream);
+/* F.interpolate(mode='bilinear', align_corners=False) (N, Hi, Wi, C) -> (N, Ho, Wo, C), any sizes; y = / += (accumulate).  The backward is a
+ * gather (every source pixel sums the destinations that read it): dx f32 = / += */
+int mtp_resize_bilinear_fwd(const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype, int64_t ldy, int64_t N, int64_t Hi, int64_t Wi,
+                            int64_t Ho, int64_t Wo, int64_t C, int accumulate, mtp_stream_t stream);
+int mtp_resize_bilinear_bwd(const void* dy, int dy_dtype, int64_t lddy, float* dx, int64_t lddx, int64_t N, int64_t Hi, int64_t Wi, int64_t Ho,
+                            int64_t Wo, int64_t C, int accumulate, mtp_stream_t stream);
+/* F.adaptive_avg_pool2d to S x S (torch's bins: floor(i H / S) .. ceil((i + 1) H / S)); y (N*S*S, C) contiguous; the backward dx f32 = / += */
+int mtp_adaptive_avg_pool_fwd(const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype, int64_t N, int64_t H, int64_t W, int64_t C,
+                              int64_t S, mtp_stream_t stream);
+int mtp_adaptive_avg_pool_bwd(const void* dy, int dy_dtype, float* dx, int64_t lddx, int64_t N, int64_t H, int64_t W, int64_t C, int64_t S,
+                              int accumulate, mtp_stream_t stream);
+/* Dropout2d with an explicit mask: y[r][c] = x[r][c] * mask[r / rows_per_sample][c]  (mask (N, C) f32 of 0 and 1 / (1 - p)) */
+int mtp_channel_scale(const void* x, int x_dtype, int64_t ldx, const float* mask, int64_t rows_per_sample, void* y, int y_dtype, int64_t ldy,
+                      int64_t rows, int64_t C, mtp_stream_t stream);
+/* mmseg's decode-head loss: logits (N*h*w, ld) ACT, K classes, resized bilinearly to the labels' (H, W) (uint8 or int64: label_bytes 1 / 8),
+ * softmax cross-entropy with ignore_index, the sum over non-ignored pixels / (N*H*W) * loss_weight (CrossEntropyLoss, avg_non_ignore=False)
+ * -> loss[0]; dlogits (N*h*w, ldd) f32 = its gradient on the low-resolution grid (the resize backward's gather).  Workspace: the caller's,
+ * >= mtp_seg_ce_workspace_bytes(N, H, W, K), 16-byte aligned.  Precondition: every label is ignore_index or in [0, K) (torch raises otherwise;
+ * mtp_amd.ops.seg_ce checks it on the host side before the launch). */
+int64_t mtp_seg_ce_workspace_bytes(int64_t N, int64_t H, int64_t W, int64_t K);
+int mtp_seg_ce(const void* logits, int dtype, int64_t ld, int64_t N, int64_t h, int64_t w, int64_t K, const void* labels, int label_bytes, int64_t H,
+               int64_t W, int ignore_index, float loss_weight, float* loss, float* dlogits, int64_t ldd, void* workspace, int64_t workspace_bytes,
+               mtp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

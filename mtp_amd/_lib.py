@@ -126,6 +126,19 @@ SIGNATURES = {
     "mtp_adamw_weight_images": (i32, [p, i32, i64, i32, p, p, p, p, p, p, f32, f32, p]),
     "mtp_adamw_flat_lr": (i32, [p, p, p, p, i64, p, p, p, i32, p, p, f32, f32, p]),
     "mtp_adamw_weight_images_lr": (i32, [p, p, i32, i64, i32, p, p, p, p, p, p, f32, f32, p]),
+    "mtp_bn_partial_rows": (i64, [i64]),
+    "mtp_bn_stats": (i32, [p, i32, i64, p, p, p, i64, i64, p]),
+    "mtp_bn_finalize": (i32, [p, p, C.c_double, p, p, f32, f32, p, p, i64, p]),
+    "mtp_bn_apply": (i32, [p, i32, i64, p, p, p, p, i32, p, i32, i64, i64, i64, p]),
+    "mtp_bn_bwd_stats": (i32, [p, i32, i64, p, i32, i64, p, p, p, p, i32, p, p, i64, i64, p]),
+    "mtp_bn_bwd_dx": (i32, [p, i32, i64, p, i32, i64, p, p, p, p, i32, p, C.c_double, p, i32, i64, i64, i64, p]),
+    "mtp_resize_bilinear_fwd": (i32, [p, i32, i64, p, i32, i64, i64, i64, i64, i64, i64, i64, i32, p]),
+    "mtp_resize_bilinear_bwd": (i32, [p, i32, i64, p, i64, i64, i64, i64, i64, i64, i64, i32, p]),
+    "mtp_adaptive_avg_pool_fwd": (i32, [p, i32, i64, p, i32, i64, i64, i64, i64, i64, p]),
+    "mtp_adaptive_avg_pool_bwd": (i32, [p, i32, p, i64, i64, i64, i64, i64, i64, i32, p]),
+    "mtp_channel_scale": (i32, [p, i32, i64, p, i64, p, i32, i64, i64, i64, p]),
+    "mtp_seg_ce_workspace_bytes": (i64, [i64, i64, i64, i64]),
+    "mtp_seg_ce": (i32, [p, i32, i64, i64, i64, i64, i64, p, i32, i64, i64, i32, f32, p, p, i64, p, i64, p]),
     "mtp_version": (C.c_char_p, []),
     "mtp_stream_create_low_priority": (i32, [p]),
     "mtp_stream_create_cu_mask": (i32, [p, i32, p]),

@@ -938,3 +938,117 @@ def copy_rows(src, dst, n):
     assert src.dtype == dst.dtype and src.shape[0] == dst.shape[0]
     check(lib().mtp_copy_rows(_p(src), src.shape[1], _p(dst), dst.shape[1], _dt(src), n, src.shape[0], _s()), "mtp_copy_rows")
     return dst
+
+
+# ------------------------------------------------------------------------------------------------ UperNet decode head (csrc/decode_head.hip)
+def _ld(t):
+    """row pitch of a 2-D row-major tensor or of a column slice of one"""
+    assert t.dim() == 2 and t.stride(1) == 1
+    return t.stride(0)
+
+
+def _pv(t):
+    """device pointer of a (possibly column-sliced) 2-D map"""
+    if not t.is_cuda:
+        raise RuntimeError("mtp_amd ops run only on an MI355X device tensor (no CPU fallback)")
+    assert t.stride(-1) == 1
+    return t.data_ptr()
+
+
+def bn_sums(x, center=None):
+    """x (rows, C) ACT (a column slice is fine) -> (2C,) f32 [sum (x - center) | sum (x - center)^2] (center (C,) f32 or None = 0), summed in a fixed
+    order (bit-identical across runs)"""
+    rows, Cc = x.shape
+    part = torch.empty(lib().mtp_bn_partial_rows(rows), 2 * Cc, device=x.device, dtype=torch.float32)
+    sums = torch.empty(2 * Cc, device=x.device, dtype=torch.float32)
+    check(lib().mtp_bn_stats(_pv(x), _dt(x), _ld(x), _f32(center), _p(part), _p(sums), rows, Cc, _s()), "mtp_bn_stats")
+    return sums
+
+
+def bn_finalize(sums, count, running_mean, running_var, mean, rstd, momentum=0.1, eps=1e-5, center=None):
+    """sums None: the eval statistics from the running ones; center: what bn_sums(x, center) was centred on"""
+    check(lib().mtp_bn_finalize(_f32(sums), _f32(center), float(count), _f32(running_mean), _f32(running_var), momentum, eps, _f32(mean), _f32(rstd), mean.numel(), _s()),
+          "mtp_bn_finalize")
+
+
+def bn_apply(x, mean, rstd, gamma, beta, y, relu=True):
+    rows, Cc = x.shape
+    assert y.shape == x.shape
+    check(lib().mtp_bn_apply(_pv(x), _dt(x), _ld(x), _f32(mean), _f32(rstd), _f32(gamma), _f32(beta), int(relu), _pv(y), _dt(y), _ld(y), rows, Cc, _s()),
+          "mtp_bn_apply")
+    return y
+
+
+def bn_bwd_sums(dy, x, mean, rstd, gamma, beta, relu=True):
+    """(2C,) f32 [sum dy' | sum dy' xhat] = [d beta | d gamma] of this batch"""
+    rows, Cc = x.shape
+    part = torch.empty(lib().mtp_bn_partial_rows(rows), 2 * Cc, device=x.device, dtype=torch.float32)
+    sums = torch.empty(2 * Cc, device=x.device, dtype=torch.float32)
+    check(lib().mtp_bn_bwd_stats(_pv(dy), _dt(dy), _ld(dy), _pv(x), _dt(x), _ld(x), _f32(mean), _f32(rstd), _f32(gamma), _f32(beta), int(relu), _p(part),
+                                 _p(sums), rows, Cc, _s()), "mtp_bn_bwd_stats")
+    return sums
+
+
+def bn_bwd_dx(dy, x, mean, rstd, gamma, beta, sums, count, dx, relu=True):
+    rows, Cc = x.shape
+    check(lib().mtp_bn_bwd_dx(_pv(dy), _dt(dy), _ld(dy), _pv(x), _dt(x), _ld(x), _f32(mean), _f32(rstd), _f32(gamma), _f32(beta), int(relu), _f32(sums),
+                              float(count), _pv(dx), _dt(dx), _ld(dx), rows, Cc, _s()), "mtp_bn_bwd_dx")
+    return dx
+
+
+def resize_bilinear_fwd(x, y, N, Hi, Wi, Ho, Wo, accumulate=False):
+    """x (N*Hi*Wi, C), y (N*Ho*Wo, C) channels-last (column slices allowed); align_corners=False"""
+    Cc = x.shape[1]
+    assert y.shape[1] == Cc and x.shape[0] == N * Hi * Wi and y.shape[0] == N * Ho * Wo
+    check(lib().mtp_resize_bilinear_fwd(_pv(x), _dt(x), _ld(x), _pv(y), _dt(y), _ld(y), N, Hi, Wi, Ho, Wo, Cc, int(accumulate), _s()),
+          "mtp_resize_bilinear_fwd")
+    return y
+
+
+def resize_bilinear_bwd(dy, dx, N, Hi, Wi, Ho, Wo, accumulate=False):
+    """dx (N*Hi*Wi, C) f32 (=/+=) from dy (N*Ho*Wo, C)"""
+    Cc = dx.shape[1]
+    assert dx.dtype == torch.float32 and dy.shape[1] == Cc and dx.shape[0] == N * Hi * Wi and dy.shape[0] == N * Ho * Wo
+    check(lib().mtp_resize_bilinear_bwd(_pv(dy), _dt(dy), _ld(dy), _pv(dx), _ld(dx), N, Hi, Wi, Ho, Wo, Cc, int(accumulate), _s()), "mtp_resize_bilinear_bwd")
+    return dx
+
+
+def adaptive_avg_pool_fwd(x, y, N, H, W, S):
+    Cc = x.shape[1]
+    assert y.shape == (N * S * S, Cc)
+    check(lib().mtp_adaptive_avg_pool_fwd(_pv(x), _dt(x), _ld(x), _p(y), _dt(y), N, H, W, Cc, S, _s()), "mtp_adaptive_avg_pool_fwd")
+    return y
+
+
+def adaptive_avg_pool_bwd(dy, dx, N, H, W, S, accumulate=False):
+    Cc = dx.shape[1]
+    assert dx.dtype == torch.float32 and dy.shape == (N * S * S, Cc)
+    check(lib().mtp_adaptive_avg_pool_bwd(_p(dy), _dt(dy), _pv(dx), _ld(dx), N, H, W, Cc, S, int(accumulate), _s()), "mtp_adaptive_avg_pool_bwd")
+    return dx
+
+
+def channel_scale(x, mask, rows_per_sample, y):
+    """Dropout2d with an explicit (N, C) f32 mask of 0 and 1 / (1 - p)"""
+    rows, Cc = x.shape
+    assert mask.shape[1] == Cc and y.shape == x.shape
+    check(lib().mtp_channel_scale(_pv(x), _dt(x), _ld(x), _f32(mask), rows_per_sample, _pv(y), _dt(y), _ld(y), rows, Cc, _s()), "mtp_channel_scale")
+    return y
+
+
+def seg_ce(logits, K, N, h, w, labels, ignore_index=255, loss_weight=1.0):
+    """logits (N*h*w, ld >= K) ACT, labels (N, H, W) uint8 / int64 -> (loss () f32, dlogits (N*h*w, ld) f32, columns K .. ld zero)"""
+    assert labels.dim() == 3 and labels.dtype in (torch.uint8, torch.int64) and labels.is_contiguous() and labels.shape[0] == N
+    H, W = labels.shape[1:]
+    ld = logits.shape[1]
+    bad = ((labels != ignore_index) & (labels.long() >= K)).any()        # (uint8 / int64 labels: only the upper bound can fail for uint8)
+    if labels.dtype == torch.int64:
+        bad = bad | ((labels != ignore_index) & (labels < 0)).any()
+    if bool(bad):
+        raise ValueError("seg_ce: labels outside [0, %d) that are not ignore_index (%d)" % (K, ignore_index))
+    ws = torch.empty((lib().mtp_seg_ce_workspace_bytes(N, H, W, K) + 3) // 4, device=logits.device, dtype=torch.float32)
+    loss = torch.empty((), device=logits.device, dtype=torch.float32)
+    dlogits = torch.zeros(logits.shape[0], ld, device=logits.device, dtype=torch.float32) if ld != K else \
+        torch.empty(logits.shape[0], ld, device=logits.device, dtype=torch.float32)
+    check(lib().mtp_seg_ce(_p(logits), _dt(logits), ld, N, h, w, K, _p(labels), labels.element_size(), H, W, int(ignore_index), float(loss_weight), _p(loss),
+                           _p(dlogits), ld, _p(ws), ws.numel() * 4, _s()), "mtp_seg_ce")
+    return loss, dlogits

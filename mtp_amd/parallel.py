@@ -160,6 +160,44 @@ class FlatParams:
         return torch.tensor(starts, dtype=torch.int64), torch.tensor(wds, dtype=torch.float32), torch.tensor(lrs, dtype=torch.float32)
 
 
+class HeadFlat:
+    """a decode head's trained parameters in one flat f32 buffer of their own (data + gradient), the parameters and their .grad re-pointed at views
+    of it as FlatParams does for the backbone: the head's gradients are exchanged, clipped and stepped as one more flat range."""
+
+    def __init__(self, head, names):
+        params = dict(head.named_parameters())
+        self.names = list(names)
+        self.offsets, self.shapes = {}, {}
+        off = 0
+        for n in self.names:
+            self.offsets[n], self.shapes[n] = off, tuple(params[n].shape)
+            off += (params[n].numel() + ALIGN - 1) // ALIGN * ALIGN
+        self.total = self.reduced = off
+        dev = params[self.names[0]].device
+        self.data = torch.zeros(off, device=dev, dtype=torch.float32)
+        self.grad = torch.zeros(off, device=dev, dtype=torch.float32)
+        self.groups = {n: 0 for n in self.names}
+        with torch.no_grad():
+            for n in self.names:
+                v = self.view(self.data, n)
+                v.copy_(params[n].detach())
+                params[n].data = v
+                params[n].grad = self.view(self.grad, n)
+        self.G = {n: self.view(self.grad, n) for n in self.names}
+
+    view = FlatParams.view
+    weight_decay_segments = FlatParams.weight_decay_segments
+    group_segments = FlatParams.group_segments
+
+
+def head_param_groups(names, shapes, weight_decay):
+    """the decode head's AdamW groups under the reference's constructors: every non-backbone name falls into layer num_max_layer - 1, i.e. lr scale 1
+    (layer_decay_optimizer_constructor_vit.py:7-16, the InternImage constructor likewise), weight decay 0 for 1-D parameters and biases"""
+    nd = [n for n in names if len(shapes[n]) <= 1 or n.endswith(".bias")]
+    dec = [n for n in names if n not in nd]
+    return [("decode_head.decay", 1.0, float(weight_decay), dec), ("decode_head.no_decay", 1.0, 0.0, nd)]
+
+
 def reference_param_groups(named_params, weight_decay, prefix="encoder."):
     """Parameter groups as LayerDecayOptimizerConstructor_ViT.add_params builds them
     (mmcv_custom/layer_decay_optimizer_constructor_vit.py:33-67): group = (layer id, decay / no_decay), created in
@@ -555,8 +593,10 @@ class FlatAdamW:
             self._rest_key = key
         return self._rest_tab if self._rest_tab is not None else ()
 
-    def step(self, norm_covered=None):
+    def step(self, norm_covered=None, extra_norm=(), sq=None):
         """returns True when the step also refreshed the engine's weight images (fuse_images).
+        extra_norm: further f32 gradient buffers whose squared norm joins the clip norm; sq: a squared norm already computed (the decode head's
+        optimizer takes the backbone optimizer's joint one).
         norm_covered: gradient tensors whose squared norm the weight-gradient launches have ALREADY added to self.sqn (BackboneEngine.backward(sqn=...)): only the
         rest of the buffer is summed here.  None: one pass over the whole gradient buffer (every world size > 1: the norm is that of the REDUCED gradients)."""
         from . import ops
@@ -566,14 +606,15 @@ class FlatAdamW:
         f = self.flat
         n = f.reduced
         gs = 1.0 / self.world
-        sq = None
-        if self.max_norm and self.max_norm > 0:
+        if sq is None and self.max_norm and self.max_norm > 0:
             rest = self._rest_table(norm_covered) if norm_covered else None
             if rest is None:
                 self.sqn.zero_()
                 ops.sqnorm(f.grad[:n], self.sqn)
             elif len(rest):
                 ops.sqnorm_segments(f.grad, rest[0], rest[1], self.sqn)
+            for g in extra_norm:          # the decode head's gradients: ONE clip norm over encoder and decoder (main_pretrain.py:786)
+                ops.sqnorm(g, self.sqn)
             sq = self.sqn
         self.sched_pending = True     # scheduler.step() of MAIN:832 happens after the save point: see __init__
         if getattr(self, "_fused", None) is not None:
@@ -590,10 +631,14 @@ class DataParallelTrainer:
     """fwd -> loss -> bwd (+ overlapped bucketed all-reduce) -> clip + AdamW, on the HIP engine."""
 
     def __init__(self, module, lr=6e-5, weight_decay=0.05, max_norm=5.0, total_steps=None, bucket_bytes=64 << 20, feature_dtype=None,
-                 comm_mode=None, comm_bf16=None, optim_wrapper=None, param_prefix="encoder."):
+                 comm_mode=None, comm_bf16=None, optim_wrapper=None, param_prefix="encoder.", decode_head=None):
         """optim_wrapper: the reference's mmengine-style dict (e.g. mtp_amd.optim_groups.pretrain_optim_wrapper('vit_l')) -- its lr, betas and weight decay
         replace the keywords, and its constructor's layer-wise lr decay groups are built with the parameter names prefixed by `param_prefix`
-        ('encoder.' as in the pretraining script, 'backbone.' as in the fine-tune frameworks).  None: the reference_param_groups optimizer."""
+        ('encoder.' as in the pretraining script, 'backbone.' as in the fine-tune frameworks).  None: the reference_param_groups optimizer.
+        decode_head: a module with loss_and_grads (mtp_amd.UPerHead) trained together with the backbone: its parameters in a flat buffer of their own
+        (HeadFlat), their gradients exchanged by the same communicator, one clip norm over both, AdamW with the same hyper-parameters and schedule
+        (head_param_groups), its BN statistics broadcast from rank 0 with the parameters, and its state under 'decode_head' in checkpoints.
+        step()'s loss_and_grads is then the head's (decode_head.loss_and_grads(labels, ...))."""
         self.module = module
         betas, groups = (0.9, 0.999), None
         if optim_wrapper is not None:
@@ -613,6 +658,14 @@ class DataParallelTrainer:
         self.opt = FlatAdamW(self.flat, lr=lr, betas=betas, weight_decay=weight_decay, max_norm=max_norm, total_steps=total_steps, world_size=self.world,
                              param_groups=groups)
         self.feature_dtype = feature_dtype
+        self.head, self.hflat, self.hopt = decode_head, None, None
+        if decode_head is not None:
+            names = decode_head.trained_parameter_names() if hasattr(decode_head, "trained_parameter_names") else \
+                [n for n, p in decode_head.named_parameters() if p.requires_grad]
+            self.hflat = HeadFlat(decode_head, names)
+            hgroups = head_param_groups(names, self.hflat.shapes, weight_decay) if groups is not None else None
+            self.hopt = FlatAdamW(self.hflat, lr=lr, betas=betas, weight_decay=weight_decay, max_norm=max_norm, total_steps=total_steps, world_size=self.world,
+                                  param_groups=hgroups)
         self.sync_replicas()
 
     def sync_replicas(self, optimizer_state=False):
@@ -622,15 +675,26 @@ class DataParallelTrainer:
         if self.world <= 1:
             return
         dist.broadcast(self.flat.data, src=0)
+        if self.head is not None:
+            dist.broadcast(self.hflat.data, src=0)
+            for b in self.head.buffers():          # BN running statistics and counters
+                dist.broadcast(b, src=0)
         if optimizer_state:
             dist.broadcast(self.opt.m, src=0)
             dist.broadcast(self.opt.v, src=0)
+            if self.head is not None:
+                dist.broadcast(self.hopt.m, src=0)
+                dist.broadcast(self.hopt.v, src=0)
+                self.hopt.t, self.hopt.last_epoch = self.opt.t, self.opt.last_epoch
             cnt = torch.tensor([self.opt.t, self.opt.last_epoch, self.opt.total_steps or 0, int(self.opt.sched_pending)], dtype=torch.int64,
                                device=self.flat.data.device)
             dist.broadcast(cnt, src=0)
             self.opt.t, self.opt.last_epoch = int(cnt[0]), int(cnt[1])
             self.opt.total_steps = int(cnt[2]) or None
             self.opt.sched_pending = bool(int(cnt[3]))
+            if self.head is not None:
+                self.hopt.t, self.hopt.last_epoch, self.hopt.total_steps, self.hopt.sched_pending = \
+                    self.opt.t, self.opt.last_epoch, self.opt.total_steps, self.opt.sched_pending
         self.engine._key = None
         self.engine._images_fresh = None
 
@@ -640,7 +704,28 @@ class DataParallelTrainer:
         return {"epoch": epoch, "iteration": self.opt.t if iteration is None else iteration,
                 "state_dict": {k: v.detach().cpu().clone() for k, v in self.module.state_dict().items()},
                 "optimizer": self.opt.state_dict(self.module), "scheduler": self.opt.scheduler_state_dict(),
-                "loss_pretrain": np.array(list(losses))}
+                "loss_pretrain": np.array(list(losses)), **self._head_checkpoint()}
+
+    def _head_checkpoint(self):
+        if self.head is None:
+            return {}
+        h, o = self.hflat, self.hopt
+        return {"decode_head": {"state_dict": {k: v.detach().cpu().clone() for k, v in self.head.state_dict().items()},
+                                "optimizer": {"names": list(h.names), "exp_avg": {n: h.view(o.m, n).cpu().clone() for n in h.names},
+                                              "exp_avg_sq": {n: h.view(o.v, n).cpu().clone() for n in h.names}, "step": o.t}}}
+
+    def _load_head(self, ck):
+        own = self.head.state_dict()
+        with torch.no_grad():
+            for k, v in ck["state_dict"].items():
+                if k in own:
+                    own[k].copy_(v)        # in place: the parameters stay views of the head's flat buffer
+            op = ck.get("optimizer")
+            if op:
+                for n in self.hflat.names:
+                    if n in op["exp_avg"]:
+                        self.hflat.view(self.hopt.m, n).copy_(op["exp_avg"][n])
+                        self.hflat.view(self.hopt.v, n).copy_(op["exp_avg_sq"][n])
 
     def save_checkpoint(self, path, **kw):
         """rank 0 writes (MAIN:823: main_process only); every rank holds identical state after the all-reduce"""
@@ -673,6 +758,11 @@ class DataParallelTrainer:
                 warnings.warn("optimizer state restored for %d of the backbone's %d trained parameters; the others restart with zero moments" % (n, want))
         if "scheduler" in ckpt:
             self.opt.load_scheduler_state_dict(ckpt["scheduler"])
+        if self.head is not None and "decode_head" in ckpt:
+            self._load_head(ckpt["decode_head"])
+        if self.head is not None:       # the head's optimizer runs in lock step with the backbone's
+            self.hopt.t, self.hopt.last_epoch, self.hopt.total_steps, self.hopt.sched_pending = \
+                self.opt.t, self.opt.last_epoch, self.opt.total_steps, self.opt.sched_pending
         self.engine._key = None
         self.engine._images_fresh = None
         self.sync_replicas(optimizer_state=True)
@@ -684,7 +774,12 @@ class DataParallelTrainer:
         self.flat.zero_accumulating()     # the engine accumulates bias / LayerNorm / table gradients; the big weight gradients are overwritten
         self.reducer.begin_step()
         feats, ctx = self.engine.forward(img, training=True, need_grad=True, feature_dtype=self.feature_dtype)
+        if self.head is not None:
+            self.hflat.grad.zero_()       # the head's loss_and_grads accumulates into the .grad views of this buffer
         loss, dfeats = loss_and_grads(feats)
+        if self.head is not None and self.reducer.active:     # the head's gradients: the backbone's communicator (or its torch.distributed fall-back)
+            for w in self.reducer._exchange(self.hflat.grad):
+                w.wait()
         # the gradient norm of the clipping step as a by-product of the weight-gradient launches (one rank only: with an exchange the norm is that of the REDUCED
         # gradients; MTP_FUSED_SQNORM=0: always the separate pass)
         fold = (self.world == 1 and not self.reducer.active and self.flat.grad.is_cuda and bool(self.opt.max_norm) and os.environ.get("MTP_FUSED_SQNORM", "1") != "0"
@@ -700,7 +795,9 @@ class DataParallelTrainer:
         wimg = getattr(self.engine, "_wimg", None)
         if getattr(self.opt, "_fused_for", 0) is not wimg:       # (first step, or the engine rebuilt its image buffers)
             self.opt.fuse_images(wimg if not getattr(self.engine, "_ls", None) else None)
-        fresh = self.opt.step(norm_covered=covered)
+        fresh = self.opt.step(norm_covered=covered, extra_norm=(self.hflat.grad,) if self.head is not None else ())
+        if self.head is not None:
+            self.hopt.step(sq=self.opt.sqn if self.opt.max_norm and self.opt.max_norm > 0 else None)
         self.engine._key = None   # parameters changed under torch's version counters: rebuild the GEMM weight images next forward ...
         if fresh and hasattr(self.engine, "mark_images_fresh"):
             self.engine.mark_images_fresh()       # ... unless the optimizer kernel has just written them (the packed ConvT / convolution weights still follow)
