@@ -42,6 +42,12 @@ def _s():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _scratch(shape, device, dtype):
+    """every workspace, partial buffer and self-allocated result of the wrappers below comes from here: plain torch.empty -- one seam, so the GPU tests can
+    hand out guarded, poisoned buffers instead (a workspace overrun is seen; an element read before it is written turns the result into NaN)"""
+    return torch.empty(shape, device=device, dtype=dtype)
+
+
 def _f32(t):
     if t is not None and t.dtype != torch.float32:
         raise TypeError("expected a float32 tensor")
@@ -78,9 +84,9 @@ def gemm_nt(a, w, out, epi=EPI_BIAS, bias=None, bias_mod=0, res=None, res_mod=0,
 
 
 def gemm_nt_tile(a, w, out, epi=EPI_BIAS, bias=None, bias_mod=0, res=None, res_mod=0, rowscale=None, rows_per_sample=0,
-                 aux=None, variant=0):
-    """tile width (256 / 128) of the kernel family gemm_nt(...) runs these arguments on (no launch)"""
-    g = _nt_args(a, w, out, epi, bias, bias_mod, res, res_mod, rowscale, rows_per_sample, aux, variant)
+                 aux=None, variant=0, n=None):
+    """tile width (256 / 128; 64 = the strip kernel) of the kernel family gemm_nt(...) runs these arguments on (no launch)"""
+    g = _nt_args(a, w, out, epi, bias, bias_mod, res, res_mod, rowscale, rows_per_sample, aux, variant, n)
     rc = lib().mtp_gemm_nt_tile(C.byref(g))
     if rc < 0:
         check(rc, "mtp_gemm_nt_tile")
@@ -128,7 +134,7 @@ def gemm_tn(a, b, out, split_k=None, use_workspace=True, variant=0, colsum=None,
     g.split_k = effective_split_k(K, a.dtype, pick_split_k(M, N, K) if split_k is None else split_k)
     g.variant = variant
     if g.split_k > 1 and use_workspace:
-        ws = torch.empty(g.split_k * M * N, device=out.device, dtype=torch.float32)   # split-K partials (summed by the callee)
+        ws = _scratch((g.split_k * M * N,), out.device, torch.float32)   # split-K partials (summed by the callee)
         g.aux = _p(ws)
         if defer is not None:     # ... or later, together with the other weight gradients of the block (sum_partials)
             g.defer_sum = 1
@@ -239,7 +245,7 @@ class WgradQueue:
             return False
         assert x.shape[0] == K and dw.dtype == torch.float32 and dw.numel() == M * N and dw.is_contiguous()
         splits = grouped_splits(K, t)
-        part = torch.empty(splits, M, N, device=dw.device, dtype=torch.float32) if splits > 1 else None
+        part = _scratch((splits, M, N), dw.device, torch.float32) if splits > 1 else None
         use_sqn = self.sqn is not None and splits == 1 and norm_ok
         self.jobs.append((dy, x, dw, colsum, splits, part, use_sqn))     # (the references keep dY / X / the partial images alive until the launch)
         if use_sqn:
@@ -331,7 +337,7 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, dx, dgamma, dbeta, beta=None, gelu=F
     # (an in-kernel f32-atomic accumulation of dgamma / dbeta was measured: 512 workgroups hitting the same 2C addresses took
     #  the kernel from 61 to 106 us; per-workgroup partials + two 8 us reductions are faster)
     nblk = lib().mtp_layernorm_bwd_partial_rows(rows)
-    part = torch.empty(nblk, 2 * Cc, device=x.device, dtype=torch.float32)     # [dgamma partials | dbeta partials] per workgroup
+    part = _scratch((nblk, 2 * Cc), x.device, torch.float32)     # [dgamma partials | dbeta partials] per workgroup
     if win_add is not None:
         # dy_eff = dy + win_add[window(row)]: the RVSA sampling heads' input gradient, added per 7 x 7 window of the (B, Hp, Wp) token grid
         B, Hp, Wp = grid
@@ -365,7 +371,7 @@ def layernorm_residual_bwd(dout, h, mean, rstd, gamma, beta, layer_scale, dh, dg
     """dh = LN'(s * layer_scale * dout); dgamma / dbeta / dls (C,) f32 ACCUMULATE the three parameter gradients (deferred with `defer`)"""
     rows, Cc = h.shape
     nblk = lib().mtp_layernorm_bwd_partial_rows(rows)
-    part = torch.empty(nblk, 3 * Cc, device=h.device, dtype=torch.float32)
+    part = _scratch((nblk, 3 * Cc), h.device, torch.float32)
     check(lib().mtp_layernorm_residual_bwd(_f32(dout), _p(h), _dt(h), _f32(mean), _f32(rstd), _f32(gamma), _f32(beta), _f32(layer_scale), _f32(sample_scale),
                                            rows_per_sample, _p(dh), part.data_ptr(), rows, Cc, _s()), "mtp_layernorm_residual_bwd")
     pair = _adjacent(dgamma, dbeta) and dgamma.numel() == Cc
@@ -646,9 +652,9 @@ def full_attn_fwd(qkv, o, lse, rel_h, rel_w, B, Hp, Wp, heads, scale):
 def full_attn_bwd(qkv, o, dout, lse, dqkv, rel_h, rel_w, drel_h, drel_w, B, Hp, Wp, heads, scale, accumulate=False, defer=None):
     hd = qkv.shape[1] // (3 * heads)
     rt = (2 * Hp - 1) + (2 * Wp - 1)
-    part = torch.empty(B * heads, rt * hd, device=qkv.device, dtype=torch.float32)
+    part = _scratch((B * heads, rt * hd), qkv.device, torch.float32)
     nws = lib().mtp_full_attn_bwd_workspace_floats(B, Hp, Wp, heads)     # > 0 beyond 256 tokens (three-pass backward)
-    ws = torch.empty(nws, device=qkv.device, dtype=torch.float32) if nws else None
+    ws = _scratch((nws,), qkv.device, torch.float32) if nws else None
     check(lib().mtp_full_attn_bwd(_p(qkv), _p(o), _p(dout), _f32(lse), _p(dqkv), _dt(qkv), _f32(rel_h), _f32(rel_w), _p(part), _p(ws),
                                   B, Hp, Wp, heads, hd, scale, _s()), "mtp_full_attn_bwd")
     if defer is not None and _adjacent(drel_h, drel_w) and drel_h.numel() == (2 * Hp - 1) * hd:
@@ -751,9 +757,9 @@ def rvsa_attn_bwd(qkv, samp, o, dout, lse, dqkv, dsamp, rel_h, rel_w, table, dre
     nh, nw = rvsa_windows(Hp, Wp)
     nblk = B * nh * nw * heads
     dev = qkv.device
-    dkv = torch.empty(T, 2 * Cc, device=dev, dtype=torch.float32)
-    rel_part = torch.empty(nblk, 26 * hd, device=dev, dtype=torch.float32)
-    tab_part = torch.empty(B * nh * nw, heads * 169, device=dev, dtype=torch.float32)     # (window, head, 169): contiguous per workgroup
+    dkv = _scratch((T, 2 * Cc), dev, torch.float32)
+    rel_part = _scratch((nblk, 26 * hd), dev, torch.float32)
+    tab_part = _scratch((B * nh * nw, heads * 169), dev, torch.float32)     # (window, head, 169): contiguous per workgroup
     check(lib().mtp_rvsa_attn_bwd(_p(qkv), _f32(samp), _p(o), _p(dout), _f32(lse), _p(dqkv), _p(dkv), _f32(dsamp), _p(rel_part), _p(tab_part),
                                   _dt(qkv), _f32(rel_h), _f32(rel_w), _f32(table), B, Hp, Wp, heads, hd, scale, _s()), "mtp_rvsa_attn_bwd")
     if defer is not None and _adjacent(drel_h, drel_w) and drel_h.numel() == 13 * hd:
@@ -861,7 +867,7 @@ def dwconv3x3_bwd_dw(dy, x, dw, db, N, H, W, accumulate=False):
     """dw (C,1,3,3) f32, db (C,) f32"""
     Cc = dy.shape[-1]
     nb = lib().mtp_dwconv3x3_bwd_dw_partial_rows(N, H, W)
-    part = torch.empty(nb, 10 * Cc, device=dy.device, dtype=torch.float32)
+    part = _scratch((nb, 10 * Cc), dy.device, torch.float32)
     check(lib().mtp_dwconv3x3_bwd_dw(_p(dy), _p(x), _dt(dy), _p(part), N, H, W, Cc, _s()), "mtp_dwconv3x3_bwd_dw")
     _reduce_pair(part, 9 * Cc, dw, db, accumulate)
 
@@ -918,7 +924,7 @@ def scale_residual_fwd(x, z, gamma, out, out_act=None, sample_scale=None, rows_p
 def scale_residual_bwd(dout, z, gamma, dz, dgamma, sample_scale=None, rows_per_sample=0, accumulate=False):
     rows, Cc = dout.shape
     nb = lib().mtp_scale_residual_bwd_partial_rows(rows)
-    part = torch.empty(nb, Cc, device=dout.device, dtype=torch.float32)
+    part = _scratch((nb, Cc), dout.device, torch.float32)
     check(lib().mtp_scale_residual_bwd(_f32(dout), _p(z), _dt(z), _f32(gamma), _f32(sample_scale), rows_per_sample, _p(dz), _p(part), rows, Cc, _s()),
           "mtp_scale_residual_bwd")
     reduce_rows(part, dgamma, accumulate)
@@ -959,8 +965,8 @@ def bn_sums(x, center=None):
     """x (rows, C) ACT (a column slice is fine) -> (2C,) f32 [sum (x - center) | sum (x - center)^2] (center (C,) f32 or None = 0), summed in a fixed
     order (bit-identical across runs)"""
     rows, Cc = x.shape
-    part = torch.empty(lib().mtp_bn_partial_rows(rows), 2 * Cc, device=x.device, dtype=torch.float32)
-    sums = torch.empty(2 * Cc, device=x.device, dtype=torch.float32)
+    part = _scratch((lib().mtp_bn_partial_rows(rows), 2 * Cc), x.device, torch.float32)
+    sums = _scratch((2 * Cc,), x.device, torch.float32)
     check(lib().mtp_bn_stats(_pv(x), _dt(x), _ld(x), _f32(center), _p(part), _p(sums), rows, Cc, _s()), "mtp_bn_stats")
     return sums
 
@@ -982,8 +988,8 @@ def bn_apply(x, mean, rstd, gamma, beta, y, relu=True):
 def bn_bwd_sums(dy, x, mean, rstd, gamma, beta, relu=True):
     """(2C,) f32 [sum dy' | sum dy' xhat] = [d beta | d gamma] of this batch"""
     rows, Cc = x.shape
-    part = torch.empty(lib().mtp_bn_partial_rows(rows), 2 * Cc, device=x.device, dtype=torch.float32)
-    sums = torch.empty(2 * Cc, device=x.device, dtype=torch.float32)
+    part = _scratch((lib().mtp_bn_partial_rows(rows), 2 * Cc), x.device, torch.float32)
+    sums = _scratch((2 * Cc,), x.device, torch.float32)
     check(lib().mtp_bn_bwd_stats(_pv(dy), _dt(dy), _ld(dy), _pv(x), _dt(x), _ld(x), _f32(mean), _f32(rstd), _f32(gamma), _f32(beta), int(relu), _p(part),
                                  _p(sums), rows, Cc, _s()), "mtp_bn_bwd_stats")
     return sums
@@ -1045,10 +1051,10 @@ def seg_ce(logits, K, N, h, w, labels, ignore_index=255, loss_weight=1.0):
         bad = bad | ((labels != ignore_index) & (labels < 0)).any()
     if bool(bad):
         raise ValueError("seg_ce: labels outside [0, %d) that are not ignore_index (%d)" % (K, ignore_index))
-    ws = torch.empty((lib().mtp_seg_ce_workspace_bytes(N, H, W, K) + 3) // 4, device=logits.device, dtype=torch.float32)
-    loss = torch.empty((), device=logits.device, dtype=torch.float32)
-    dlogits = torch.zeros(logits.shape[0], ld, device=logits.device, dtype=torch.float32) if ld != K else \
-        torch.empty(logits.shape[0], ld, device=logits.device, dtype=torch.float32)
+    ws = _scratch(((lib().mtp_seg_ce_workspace_bytes(N, H, W, K) + 3) // 4,), logits.device, torch.float32)
+    loss = _scratch((), logits.device, torch.float32)
+    dlogits = _scratch((logits.shape[0], ld), logits.device, torch.float32).zero_() if ld != K else \
+        _scratch((logits.shape[0], ld), logits.device, torch.float32)
     check(lib().mtp_seg_ce(_p(logits), _dt(logits), ld, N, h, w, K, _p(labels), labels.element_size(), H, W, int(ignore_index), float(loss_weight), _p(loss),
                            _p(dlogits), ld, _p(ws), ws.numel() * 4, _s()), "mtp_seg_ce")
     return loss, dlogits

@@ -24,6 +24,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from .. import _lib
+from .. import ops as _ops
 from ..ops import _dt, _s, lib
 
 
@@ -84,7 +85,7 @@ def dcnv3_forward(input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, p
         raise RuntimeError("offset / mask must be (N, %d, %d, group*P*2) / (N, %d, %d, group*P) with P = %d" % (Ho, Wo, Ho, Wo, P))
     half = input.dtype == torch.float16
     input, offset, mask = _as_f32(input, offset, mask)
-    output = torch.empty((N, Ho, Wo, group * group_channels), dtype=input.dtype, device=input.device)
+    output = _ops._scratch((N, Ho, Wo, group * group_channels), input.device, input.dtype)
     _lib.check(lib().mtp_dcnv3_fwd(input.data_ptr(), offset.data_ptr(), mask.data_ptr(), output.data_ptr(), _dtc(input), C.byref(g), _s()), "mtp_dcnv3_fwd")
     return output.half() if half else output
 
@@ -97,9 +98,9 @@ def dcnv3_backward(input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, 
     Ho, Wo = out_size(g)
     if tuple(grad_output.shape) != (input.shape[0], Ho, Wo, group * group_channels):
         raise RuntimeError("grad_output must be (N, %d, %d, %d)" % (Ho, Wo, group * group_channels))
-    kw = dict(dtype=torch.float64 if input.dtype == torch.float64 else torch.float32, device=input.device)
+    gdt = torch.float64 if input.dtype == torch.float64 else torch.float32
     input, offset, mask, grad_output = _as_f32(input, offset, mask, grad_output)
-    grad_input, grad_offset, grad_mask = torch.empty(input.shape, **kw), torch.empty(offset.shape, **kw), torch.empty(mask.shape, **kw)
+    grad_input, grad_offset, grad_mask = (_ops._scratch(tuple(t.shape), input.device, gdt) for t in (input, offset, mask))
     _lib.check(lib().mtp_dcnv3_bwd(input.data_ptr(), offset.data_ptr(), mask.data_ptr(), grad_output.data_ptr(), _dtc(input), grad_input.data_ptr(),
                                    grad_offset.data_ptr(), grad_mask.data_ptr(), C.byref(g), _s()), "mtp_dcnv3_bwd")
     return [grad_input, grad_offset, grad_mask]
@@ -115,9 +116,8 @@ def dcnv3_backward_act(input, offset, mask, kernel_h, kernel_w, stride_h, stride
     Ho, Wo = out_size(g)
     if tuple(grad_output.shape) != (input.shape[0], Ho, Wo, group * group_channels):
         raise RuntimeError("grad_output must be (N, %d, %d, %d)" % (Ho, Wo, group * group_channels))
-    kw = dict(dtype=torch.float32, device=input.device)
-    grad_input, grad_offset, grad_mask = torch.empty(input.shape, **kw), torch.empty(offset.shape, **kw), torch.empty(mask.shape, **kw)
-    act = torch.empty(input.shape[0] * Ho * Wo, act_ld, dtype=input.dtype, device=input.device)
+    grad_input, grad_offset, grad_mask = (_ops._scratch(tuple(t.shape), input.device, torch.float32) for t in (input, offset, mask))
+    act = _ops._scratch((input.shape[0] * Ho * Wo, act_ld), input.device, input.dtype)
     rc = lib().mtp_dcnv3_bwd_act(input.data_ptr(), offset.data_ptr(), mask.data_ptr(), grad_output.data_ptr(), _dt(input), grad_input.data_ptr(),
                                  grad_offset.data_ptr(), grad_mask.data_ptr(), act.data_ptr(), act_ld, C.byref(g), _s())
     if rc == -2:      # MTP_ERR_UNSUPPORTED: no gather-form backward for this geometry, nothing was launched

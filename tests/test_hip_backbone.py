@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import guard
 import mtp_amd
 import recipe
 from conftest import record_parity, rel_err
@@ -13,6 +14,25 @@ from oracle import vit_rvsa_oracle as O
 
 pytestmark = pytest.mark.gpu
 t = torch.from_numpy
+ARENA = None     # the running test's guard.Arena
+
+
+@pytest.fixture(autouse=True)
+def arena(monkeypatch):
+    """the op-level tests take their outputs (poisoned, between guards) from a fresh arena and freeze their inputs; in every test the wrappers' own
+    workspaces (ops._scratch) are poisoned and guarded.  The models' and engines' own tensors are left alone.  Teardown compares every guard and
+    frozen input bit for bit."""
+    global ARENA
+    from mtp_amd import ops as _o
+    ARENA = a = guard.Arena("cuda")
+    monkeypatch.setattr(_o, "_scratch", a.scratch)
+    yield a
+    ARENA = None
+    torch.cuda.synchronize()
+    try:
+        a.check()
+    finally:
+        a.close()
 
 
 def build(embed_dim, depth, heads, interval, out_indices, precision, **kw):
@@ -198,18 +218,19 @@ def test_full_size_roundtrip_properties_vit_l_shapes():
     w = (torch.randint(-64, 65, (3 * C, C), device="cuda", generator=g).float() / 64).to(torch.bfloat16)
     s_bf = (a.float() + b.float()).to(torch.bfloat16)
     assert torch.equal(s_bf.float(), a.float() + b.float())           # the sum itself is exact in bf16 on this grid
+    ARENA.frozen(a, b, w, s_bf)
     for variant in (0, 1024):
-        ya = ops.gemm_nt(a, w, torch.empty(T, 3 * C, device="cuda"), variant=variant)
-        yb = ops.gemm_nt(b, w, torch.empty(T, 3 * C, device="cuda"), variant=variant)
-        ys = ops.gemm_nt(s_bf, w, torch.empty(T, 3 * C, device="cuda"), variant=variant)
+        ya = ops.gemm_nt(a, w, ARENA.empty(T, 3 * C), variant=variant)
+        yb = ops.gemm_nt(b, w, ARENA.empty(T, 3 * C), variant=variant)
+        ys = ops.gemm_nt(s_bf, w, ARENA.empty(T, 3 * C), variant=variant)
         assert torch.equal(ya + yb, ys), variant
         # a few rows against an f64 host dot product: exact, too
         idx = torch.tensor([0, 1, 777, 6000, T - 1])
         ref = a[idx].double().cpu() @ w.double().cpu().t()
         assert torch.equal(ya[idx].double().cpu(), ref), variant
-    assert ops.gemm_nt_tile(a, w, torch.empty(T, 3 * C, device="cuda")) == 256
-    f = ops.tokens_to_nchw(a, torch.empty(64, C, 14, 14, device="cuda", dtype=torch.bfloat16), 64, 14, 14, 0)
-    assert torch.equal(ops.nchw_to_tokens(f, torch.empty_like(a), 64, 14, 14, 0), a)
+    assert ops.gemm_nt_tile(a, w, ARENA.empty(T, 3 * C)) == 256
+    f = ops.tokens_to_nchw(a, ARENA.empty(64, C, 14, 14, dtype=torch.bfloat16), 64, 14, 14, 0)
+    assert torch.equal(ops.nchw_to_tokens(f, ARENA.empty(*a.shape, dtype=a.dtype), 64, 14, 14, 0), a)
 
 
 def _l2(v, ref):

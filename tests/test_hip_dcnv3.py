@@ -4,13 +4,35 @@ several channel counts), plus bf16, the autograd Function and InternImage-sized 
 import pytest
 import torch
 
+import guard
+
 from test_dcnv3_oracle import CASES, load_case, rel
 
 pytestmark = pytest.mark.gpu
 
 
+ARENA = None     # the running test's guard.Arena
+
+
+@pytest.fixture(autouse=True)
+def arena(monkeypatch):
+    """the operator allocates its own outputs (ops._scratch): under the arena they come poisoned and between guards, checked at teardown with the frozen inputs"""
+    global ARENA
+    from mtp_amd import ops as _o
+    ARENA = a = guard.Arena("cuda")
+    monkeypatch.setattr(_o, "_scratch", a.scratch)
+    yield a
+    ARENA = None
+    torch.cuda.synchronize()
+    try:
+        a.check()
+    finally:
+        a.close()
+
+
 def dev(t, dtype=torch.float32):
-    return t.to(dtype).cuda().contiguous()
+    """an operator INPUT: frozen"""
+    return ARENA.frozen(t.to(dtype).cuda().contiguous())
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -36,7 +58,7 @@ def test_bf16_vs_oracle_on_the_same_rounded_inputs(name):
     r = {k: t[k].to(torch.bfloat16) for k in ("input", "offset", "mask", "grad_output")}
     ref_y = D.dcnv3_forward(r["input"].double(), r["offset"].double(), r["mask"].double(), *args, rmc)
     ref_g = D.dcnv3_backward(r["input"].double(), r["offset"].double(), r["mask"].double(), *args, r["grad_output"].double(), rmc)
-    x, off, m, G = (r[k].cuda().contiguous() for k in ("input", "offset", "mask", "grad_output"))
+    x, off, m, G = ARENA.frozen(*(r[k].cuda().contiguous() for k in ("input", "offset", "mask", "grad_output")))
     y = dcnv3_forward(x, off, m, *args, 256, rmc)
     assert y.dtype == torch.bfloat16 and rel(y.double().cpu(), ref_y) < 6e-3          # one bf16 rounding of the output
     grads = dcnv3_backward(x, off, m, *args, G, 256, rmc)
@@ -55,7 +77,7 @@ def test_float16_runs_on_the_f32_kernels_and_float64_on_double_kernels(name):
     r = {k: t[k].to(torch.float16) for k in ("input", "offset", "mask", "grad_output")}
     ref_y = D.dcnv3_forward(r["input"].double(), r["offset"].double(), r["mask"].double(), *args, rmc)
     ref_g = D.dcnv3_backward(r["input"].double(), r["offset"].double(), r["mask"].double(), *args, r["grad_output"].double(), rmc)
-    x, off, m, G = (r[k].cuda().contiguous() for k in ("input", "offset", "mask", "grad_output"))
+    x, off, m, G = ARENA.frozen(*(r[k].cuda().contiguous() for k in ("input", "offset", "mask", "grad_output")))
     y = dcnv3_forward(x, off, m, *args, 256, rmc)
     assert y.dtype == torch.float16 and rel(y.double().cpu(), ref_y) < 1e-3          # one float16 rounding of the output
     for g, rg in zip(dcnv3_backward(x, off, m, *args, G, 256, rmc), ref_g):
@@ -66,7 +88,7 @@ def test_float16_runs_on_the_f32_kernels_and_float64_on_double_kernels(name):
     d = {k: t[k].double() for k in ("input", "offset", "mask", "grad_output")}
     ref_y = D.dcnv3_forward(d["input"], d["offset"], d["mask"], *args, rmc)
     ref_g = D.dcnv3_backward(d["input"], d["offset"], d["mask"], *args, d["grad_output"], rmc)
-    xd, od, md, Gd = (d[k].cuda().contiguous() for k in ("input", "offset", "mask", "grad_output"))
+    xd, od, md, Gd = ARENA.frozen(*(d[k].cuda().contiguous() for k in ("input", "offset", "mask", "grad_output")))
     yd = dcnv3_forward(xd, od, md, *args, 256, rmc)
     assert yd.dtype == torch.float64 and rel(yd.cpu(), ref_y) < 1e-12
     for g, rg in zip(dcnv3_backward(xd, od, md, *args, Gd, 256, rmc), ref_g):
@@ -113,6 +135,7 @@ def test_internimage_sized_level_properties():
     off = (torch.rand(N, H, W, M * P * 2, device="cuda") - 0.5) * 6
     m = torch.softmax(torch.randn(N, H, W, M, P, device="cuda"), -1).reshape(N, H, W, M * P)
     G = torch.randn(N, H, W, M * Dg, device="cuda")
+    ARENA.frozen(x, off, m, G)
     y = dcnv3_forward(x, off, m, *args, 256, 0)
     gi, go, gm = dcnv3_backward(x, off, m, *args, G, 256, 0)
     s = (y.double() * G.double()).sum()
@@ -144,6 +167,7 @@ def test_gather_form_backward_equals_the_scatter_form(shape, osc, amp, rmc, dtyp
     m = torch.softmax(torch.randn(N, H, W, M, P, device="cuda"), -1).reshape(N, H, W, M * P).to(dtype)
     G = torch.randn(N, H, W, M * 16, device="cuda").to(dtype)
     monkeypatch.setenv("MTP_DCNV3_VARIANT", "2")
+    ARENA.frozen(x, off, m, G)
     ref = dcnv3_backward(x, off, m, *args, G, 256, rmc)
     for variant in ("0", "4"):       # 0: the window form; 4: the 3 x 3 form where offset_scale is 1 or 2 (else the window form)
         monkeypatch.setenv("MTP_DCNV3_VARIANT", variant)
@@ -167,6 +191,7 @@ def test_backward_writes_grad_offset_as_gemm_operand(dtype, M, rmc, ld):
     off = ((torch.rand(N, H, W, M * P * 2, device="cuda") - 0.5) * 3).to(dtype)
     m = torch.softmax(torch.randn(N, H, W, M, P, device="cuda"), -1).reshape(N, H, W, M * P).to(dtype)
     G = torch.randn(N, H, W, M * 16, device="cuda").to(dtype)
+    ARENA.frozen(x, off, m, G)
     ref = dcnv3_backward(x, off, m, *args, G, 256, rmc)
     gi, go, gm, act = dcnv3_backward_act(x, off, m, *args, G, 256, ld, rmc)
     assert rel(gi, ref[0]) < 2e-6 and torch.equal(go, ref[1]) and torch.equal(gm, ref[2])
@@ -189,6 +214,7 @@ def test_bf16_matches_fp32_at_internimage_size():
     off = ((torch.rand(N, H, W, M * P * 2, device="cuda") - 0.5) * 4).bfloat16()
     m = torch.softmax(torch.randn(N, H, W, M, P, device="cuda"), -1).reshape(N, H, W, M * P).bfloat16()
     G = torch.randn(N, H, W, M * Dg, device="cuda").bfloat16()
+    ARENA.frozen(x, off, m, G)
     y16 = dcnv3_forward(x, off, m, *args, 256, 0)
     y32 = dcnv3_forward(x.float(), off.float(), m.float(), *args, 256, 0)
     assert rel(y16.float(), y32) < 6e-3

@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import guard
 import mtp_amd
 from conftest import ROOT, record_parity, rel_err
 from mtp_amd import ops as OPS
@@ -28,12 +29,39 @@ def rnd(*shape, seed=0, scale=1.0):
     return scale * torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
 
 
+ARENA = None     # the running test's guard.Arena
+
+
+@pytest.fixture(autouse=True)
+def arena(monkeypatch):
+    """the operator tests' outputs come poisoned and between guards out of a fresh arena, their inputs are frozen, and the wrappers' own workspaces
+    (ops._scratch; the backbone tests' too) are poisoned and guarded; teardown compares every guard and frozen input bit for bit"""
+    global ARENA
+    from mtp_amd import ops as _o
+    ARENA = a = guard.Arena("cuda")
+    monkeypatch.setattr(_o, "_scratch", a.scratch)
+    yield a
+    ARENA = None
+    torch.cuda.synchronize()
+    try:
+        a.check()
+    finally:
+        a.close()
+
+
 def dev(t, dtype=None):
-    return t.to("cuda", dtype or t.dtype).contiguous()
+    """an op INPUT on the device: guarded and frozen"""
+    return ARENA.frozen(ARENA.like(t, dtype=dtype or t.dtype))
+
+
+def io(t, dtype=None):
+    """a tensor an op updates in place by contract (accumulate=True, the accumulating gradient outputs): guarded, not frozen"""
+    return ARENA.like(t, dtype=dtype or t.dtype)
 
 
 def e(*shape, dtype=torch.float32):
-    return torch.empty(*shape, device="cuda", dtype=dtype)
+    """an op OUTPUT: NaN-poisoned, between guards"""
+    return ARENA.empty(*shape, dtype=dtype)
 
 
 def _l2(a, b):
@@ -68,12 +96,12 @@ def test_conv3x3_as_im2col_gemm_forward_and_gradients(dtype, N, H, W, Cin, Cout,
     dy = rnd(N * Ho * Wo, Cout, seed=4)
     ref.backward(dy.to(dtype).float().reshape(N, Ho, Wo, Cout).permute(0, 3, 1, 2))
     dya = dev(dy, dtype)
-    dw2, db = e(Cout, Kp), torch.zeros(Cout, device="cuda")
+    dw2, db = e(Cout, Kp), ARENA.zeros(Cout)
     OPS.gemm_tn(dya, cols, dw2, colsum=db)
     dw = OPS.conv3x3_unpack_grad(dw2, e(Cout, Cin, 3, 3))
     assert rel_err(dw.cpu(), wr.grad) < TOL[dtype] and rel_err(db.cpu(), br.grad) < TOL[dtype]
     dcols = OPS.gemm_nt(dya, w2t, e(N * Ho * Wo, Kp, dtype=dtype))
-    dx = torch.full((N, Cin, H, W) if nchw else (N, H, W, Cin), 7.0, device="cuda")
+    dx = io(torch.full((N, Cin, H, W) if nchw else (N, H, W, Cin), 7.0))
     OPS.col2im3x3(dcols, dx, strides, N, H, W, Cin, stride)
     got = dx.cpu() if nchw else dx.cpu().permute(0, 3, 1, 2)
     assert rel_err(got, xr.grad) < TOL[dtype]
@@ -94,10 +122,10 @@ def test_depthwise_conv3x3_forward_and_gradients(dtype, N, H, W, C):
     ref.backward(dy)
     dya = dev(dy.reshape(-1, C), dtype)
     base = rnd(N * H * W, C, seed=5)
-    dx = OPS.dwconv3x3_bwd_dx(dya, dev(w), dev(base), N, H, W, accumulate=True)
+    dx = OPS.dwconv3x3_bwd_dx(dya, dev(w), io(base), N, H, W, accumulate=True)
     assert rel_err(dx.cpu(), base + xr.grad.reshape(-1, C)) < TOL[dtype]
     assert rel_err(OPS.dwconv3x3_bwd_dx(dya, dev(w), e(N * H * W, C), N, H, W).cpu(), xr.grad.reshape(-1, C)) < TOL[dtype]
-    dw, db = torch.zeros(C, 1, 3, 3, device="cuda"), torch.zeros(C, device="cuda")
+    dw, db = e(C, 1, 3, 3), e(C)      # (accumulate=False: both are overwritten)
     OPS.dwconv3x3_bwd_dw(dya, xa, dw, db, N, H, W)
     assert rel_err(dw.cpu(), wr.grad) < TOL[dtype] and rel_err(db.cpu(), br.grad) < TOL[dtype]
 
@@ -117,10 +145,10 @@ def test_depthwise_conv_kxk_forward_and_gradients(dtype, N, H, W, C, k):
     ref.backward(dy)
     dya = dev(dy.reshape(-1, C), dtype)
     base = rnd(N * H * W, C, seed=5)
-    dx = OPS.dwconv_bwd_dx(dya, dev(w), dev(base), N, H, W, k, accumulate=True)
+    dx = OPS.dwconv_bwd_dx(dya, dev(w), io(base), N, H, W, k, accumulate=True)
     assert rel_err(dx.cpu(), base + xr.grad.reshape(-1, C)) < TOL[dtype]
     assert rel_err(OPS.dwconv_bwd_dx(dya, dev(w), e(N * H * W, C), N, H, W, k).cpu(), xr.grad.reshape(-1, C)) < TOL[dtype]
-    dw, db = torch.zeros(C, 1, k, k, device="cuda"), torch.zeros(C, device="cuda")
+    dw, db = ARENA.zeros(C, 1, k, k), ARENA.zeros(C)
     OPS.dwconv_bwd_dw(dya, xa, dw, db, N, H, W, k)
     assert rel_err(dw.cpu(), wr.grad) < TOL[dtype] and rel_err(db.cpu(), br.grad) < TOL[dtype]
     if k == 3:
@@ -143,7 +171,7 @@ def test_center_feature_scale_forward_and_gradients(dtype, rows, G, GC, ld):
     lpad[:, :G] = lg
     out = OPS.center_feature_scale_fwd(dev(y, dtype), dev(xp, dtype), dev(lpad, dtype), e(rows, C, dtype=dtype), G)
     assert rel_err(out.float().cpu(), ref.detach()) < TOL[dtype]
-    dy, dxp, dl = e(rows, C, dtype=dtype), e(rows, C), torch.full((rows, ld), 7.0, device="cuda", dtype=dtype)
+    dy, dxp, dl = e(rows, C, dtype=dtype), e(rows, C), io(torch.full((rows, ld), 7.0), dtype)
     OPS.center_feature_scale_bwd(dev(dout, dtype), dev(y, dtype), dev(xp, dtype), dev(lpad, dtype), dy, dxp, dl, G)
     assert rel_err(dy.float().cpu(), yr.grad) < TOL[dtype] and rel_err(dxp.cpu(), xr.grad) < TOL[dtype]
     assert rel_err(dl[:, :G].float().cpu(), lr.grad) < TOL[dtype] and float(dl[:, G:].float().abs().max() if ld > G else 0.0) == 0.0
@@ -161,7 +189,7 @@ def test_softmax_over_the_points_of_each_group(dtype, rows, G, P, ld):
     # the backward recomputes from the stored (rounded) probabilities: compare with autograd at those probabilities
     pq = prob.float().cpu().reshape(rows, G, P)
     want = (pq * (dp.reshape(rows, G, P) - (pq * dp.reshape(rows, G, P)).sum(-1, keepdim=True))).reshape(rows, G * P)
-    dl = torch.full((rows, ld), 3.0, device="cuda", dtype=dtype)
+    dl = io(torch.full((rows, ld), 3.0), dtype)
     OPS.softmax_groups_bwd(prob, dev(dp), dl, G, P)
     assert rel_err(dl[:, :G * P].float().cpu(), want) < TOL[dtype]
     assert float(dl[:, G * P:].float().abs().max()) == 0.0 if ld > G * P else True
@@ -182,7 +210,7 @@ def test_layer_scale_residual_forward_and_gradients(dtype, rows, C, rps):
     assert rel_err(out.cpu(), ref) < 1e-6 and rel_err(outa.float().cpu(), ref) < TOL[dtype]
     do = rnd(rows, C, seed=4)
     ref.backward(do)
-    dg = torch.zeros(C, device="cuda")
+    dg = e(C)      # (accumulate=False: overwritten)
     dz = OPS.scale_residual_bwd(dev(do), dev(z, dtype), dev(gamma), e(rows, C, dtype=dtype), dg, None if s is None else dev(s), rps)
     assert rel_err(dz.float().cpu(), zr.grad) < TOL[dtype] and rel_err(dg.cpu(), gr.grad) < 1e-4
 
@@ -218,11 +246,11 @@ def test_layernorm_residual_fused_fwd_bwd(dtype, rows, C):
     ref = x + ss.repeat_interleave(rps)[:rows, None] * lr * torch.nn.functional.layer_norm(hr, (C,), gr, br, 1e-6)
     ref.backward(dout)
     out, oact, mean, rstd = e(rows, C), e(rows, C, dtype=dtype), e(rows), e(rows)
-    OPS.layernorm_residual_fwd(dev(h).to(dtype), dev(g), dev(b), dev(x), dev(ls), out, oact, mean, rstd, dev(ss), rps)
+    OPS.layernorm_residual_fwd(dev(h, dtype), dev(g), dev(b), dev(x), dev(ls), out, oact, mean, rstd, dev(ss), rps)
     tol = 1e-5 if dtype == torch.float32 else 1e-2
     assert rel_err(out.cpu(), ref.detach()) < 1e-5 and rel_err(oact.float().cpu(), ref.detach()) < tol
-    dh, dg, db, dl = e(rows, C, dtype=dtype), torch.zeros(C, device="cuda"), torch.zeros(C, device="cuda"), torch.zeros(C, device="cuda")
-    OPS.layernorm_residual_bwd(dev(dout), dev(h).to(dtype), mean, rstd, dev(g), dev(b), dev(ls), dh, dg, db, dl, dev(ss), rps)
+    dh, dg, db, dl = e(rows, C, dtype=dtype), ARENA.zeros(C), ARENA.zeros(C), ARENA.zeros(C)
+    OPS.layernorm_residual_bwd(dev(dout), dev(h, dtype), mean, rstd, dev(g), dev(b), dev(ls), dh, dg, db, dl, dev(ss), rps)
     assert rel_err(dh.float().cpu(), hr.grad) < (1e-4 if dtype == torch.float32 else 1e-2)
     assert rel_err(dg.cpu(), gr.grad) < 1e-4 and rel_err(db.cpu(), br.grad) < 1e-4 and rel_err(dl.cpu(), lr.grad) < 1e-4
 

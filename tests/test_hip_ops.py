@@ -5,6 +5,7 @@ import os
 import pytest
 import torch
 
+import guard
 from conftest import ROOT, rel_err
 from oracle import vit_rvsa_oracle as O
 
@@ -27,12 +28,39 @@ def rnd(*shape, dtype=torch.float32, scale=1.0, seed=0):
     return t.to(dtype).float() if dtype == torch.bfloat16 else t    # values exactly representable in the op's dtype
 
 
+ARENA = None     # the running test's guard.Arena (set by the autouse fixture below)
+
+
+@pytest.fixture(autouse=True)
+def arena(monkeypatch):
+    """every buffer of a test comes out of a fresh arena: outputs poisoned and between guards, inputs frozen, the wrappers' own workspaces
+    (ops._scratch) poisoned and guarded too; at teardown every guard and every frozen input is compared bit for bit"""
+    global ARENA
+    from mtp_amd import ops as o
+    ARENA = a = guard.Arena("cuda")
+    monkeypatch.setattr(o, "_scratch", a.scratch)
+    yield a
+    ARENA = None
+    torch.cuda.synchronize()
+    try:
+        a.check()
+    finally:
+        a.close()
+
+
 def dev(t, dtype=None):
-    return t.to("cuda", dtype=dtype or t.dtype).contiguous()
+    """an op INPUT on the device: guarded, and frozen -- no op may change it"""
+    return ARENA.frozen(ARENA.like(t, dtype=dtype or t.dtype))
+
+
+def io(t, dtype=None):
+    """a tensor an op updates in place by contract (accumulation target, parameter under the optimizer): guarded, not frozen"""
+    return ARENA.like(t, dtype=dtype or t.dtype)
 
 
 def e(*shape, dtype=torch.float32):
-    return torch.empty(*shape, device="cuda", dtype=dtype)
+    """an op OUTPUT: NaN-poisoned, between guards -- the op must write every element and nothing else"""
+    return ARENA.empty(*shape, dtype=dtype)
 
 
 # ------------------------------------------------------------------------------------------------ GEMM
@@ -301,7 +329,7 @@ def test_gemm_tn_bias_gradient_byproduct(ops, dtype, Kc, M, N, split):
     otherwise; both ACCUMULATE (Linear bias gradient, VIT:50-52 backward)."""
     a, b = rnd(Kc, M, dtype=dtype, scale=0.5), rnd(Kc, N, dtype=dtype, seed=1, scale=0.5)
     cs0 = rnd(M, seed=2)
-    cs = dev(cs0)
+    cs = io(cs0)
     out = ops.gemm_tn(dev(a, dtype), dev(b, dtype), e(M, N), split_k=split, colsum=cs)
     assert rel_err(out.cpu(), a.t() @ b) < 3e-4
     assert rel_err(cs.cpu(), cs0 + a.sum(0)) < 1e-4
@@ -314,7 +342,7 @@ def _wgrad_group(ops, shapes, seed=0):
         a = rnd(Kc, M, dtype=torch.bfloat16, scale=0.5, seed=seed + i)
         b = rnd(Kc, N, dtype=torch.bfloat16, seed=seed + 50 + i, scale=0.5)
         cs0 = rnd(M, seed=seed + 90 + i) if with_cs else None
-        dw, cs = e(M, N), (dev(cs0) if with_cs else None)
+        dw, cs = e(M, N), (io(cs0) if with_cs else None)
         dw.fill_(float("nan"))                                   # the launch must overwrite every element
         assert q.add(dev(a, torch.bfloat16), dev(b, torch.bfloat16), dw, cs)
         refs.append((a, b, cs0, dw, cs))
@@ -370,7 +398,7 @@ def test_gemm_tn_grouped_vit_l_block_repeatable(ops, variant):
         q = ops.WgradQueue(variant=variant)
         outs = []
         for (a, b), (K, M, N, _) in zip(ins, shapes):
-            dw, cs = e(M, N), torch.zeros(M, device="cuda")
+            dw, cs = e(M, N), ARENA.zeros(M)
             assert q.add(a, b, dw, cs)
             outs.append((dw, cs))
         q.flush()
@@ -378,7 +406,7 @@ def test_gemm_tn_grouped_vit_l_block_repeatable(ops, variant):
         if first is None:
             first = outs
             for (a, b), (dw, cs) in zip(ins, outs):
-                ref, rcs = e(*dw.shape), torch.zeros_like(cs)
+                ref, rcs = e(*dw.shape), ARENA.zeros(*cs.shape)
                 ops.gemm_tn(a, b, ref, colsum=rcs)
                 assert rel_err(dw, ref) < 2e-5 and rel_err(cs, rcs) < 2e-5
         else:
@@ -422,7 +450,7 @@ def test_gemm_tn_deferred_partial_sums(ops, dtype):
 def test_weight_images_one_launch(ops, dtype):
     """every GEMM-side image (W, W^T in ACT; stacked f32 head weights / biases) out of one descriptor-table launch"""
     ws = [rnd(192, 128, seed=1), rnd(64, 256, seed=2), rnd(100, 36, seed=3), rnd(32, 128, seed=4), rnd(16, 128, seed=5), rnd(1, 32, seed=6)]
-    dws = [dev(w) for w in ws]
+    dws = [io(w) if i == 1 else dev(w) for i, w in enumerate(ws)]      # (ws[1] is updated in place below, as the optimizer does)
     stack, bias = e(48, 128), e(32)
     imgs = [(e(192, 128, dtype=dtype), e(128, 192, dtype=dtype)), (None, e(256, 64, dtype=dtype)), (e(100, 36, dtype=dtype), e(36, 100, dtype=dtype))]
     entries = [(dws[0], imgs[0][0], imgs[0][1], False), (dws[1], None, imgs[1][1], False), (dws[2], imgs[2][0], imgs[2][1], False),
@@ -468,7 +496,7 @@ def test_layernorm_fwd_bwd(ops, dtype, rows, C):
     assert rel_err(dx.cpu(), tot) < 2e-4 and rel_err(dxc.float().cpu(), tot * cs.repeat_interleave(rps)[:, None]) < TOL[dtype]
     assert rel_err(dg.cpu(), dgr) < 2e-4 and rel_err(db.cpu(), dbr) < 2e-4
     # accumulating entry point (training engine): dgamma / dbeta += ..., no partial buffer
-    dg2, db2, dx2 = dev(torch.ones(C)), dev(torch.full((C,), -2.0)), e(rows, C)
+    dg2, db2, dx2 = io(torch.ones(C)), io(torch.full((C,), -2.0)), e(rows, C)
     ops.layernorm_bwd(dev(dy, dtype), dev(x), mean, rstd, dev(g), dx2, dg2, db2, dres=dev(dres), extra=dev(extra), accumulate=True)
     assert rel_err(dg2.cpu(), 1 + dgr) < 2e-4 and rel_err(db2.cpu(), dbr - 2) < 2e-4 and rel_err(dx2.cpu(), tot) < 2e-4
 
@@ -480,7 +508,7 @@ def test_layernorm_bwd_deferred_parameter_gradients(ops):
         x, g = rnd(rows, C, scale=2.0, seed=10 * j) + 0.5, 1 + 0.1 * rnd(C, seed=10 * j + 1)
         _, mr, rr = O.layernorm_fwd(x, g, torch.zeros(C))
         dy = rnd(rows, C, seed=10 * j + 3)
-        gb = dev(torch.full((2 * C,), float(j)))          # [dgamma | dbeta] adjacent, as in the flat gradient buffer
+        gb = io(torch.full((2 * C,), float(j)))          # [dgamma | dbeta] adjacent, as in the flat gradient buffer
         ops.layernorm_bwd(dev(dy), dev(x), dev(mr), dev(rr), dev(g), e(rows, C), gb[:C], gb[C:], accumulate=True, defer=items)
         _, dgr, dbr = O.layernorm_bwd(dy, x, mr, rr, g)
         want.append(torch.cat([dgr, dbr]) + j)
@@ -524,14 +552,14 @@ def test_colsum_reduce_rows_axpy_cast(ops, dtype):
     assert rel_err(ops.reduce_rows(dev(part), e(260)).cpu(), part.sum(0)) < 2e-4
     # column slice of a wider partial buffer, accumulating into a non-zero gradient (partials -> two parameters, no staging copy)
     dpart, g0 = dev(part), rnd(160, seed=3)
-    acc = ops.reduce_rows(dpart[:, 100:], dev(g0), accumulate=True)
+    acc = ops.reduce_rows(dpart[:, 100:], io(g0), accumulate=True)
     assert rel_err(acc.cpu(), g0 + part[:, 100:].sum(0)) < 2e-4
     srcs = [rnd(n, seed=20 + i) for i, n in enumerate((32 * 128, 5, 16 * 128, 1, 700, 64))]
     dsts = [e(n) for n in (32 * 128, 5, 16 * 128, 1, 700, 64)]
     ops.copy_segments([dev(s) for s in srcs], dsts)
     assert all(torch.equal(d.cpu(), s) for s, d in zip(srcs, dsts))
     y, x = rnd(1001), rnd(1001, seed=9)
-    assert rel_err(ops.axpy(dev(y), dev(x), 0.5).cpu(), y + 0.5 * x) < 1e-6
+    assert rel_err(ops.axpy(io(y), dev(x), 0.5).cpu(), y + 0.5 * x) < 1e-6
     src = rnd(1027)
     assert torch.equal(ops.cast(dev(src), e(1027, dtype=torch.bfloat16)).cpu(), src.to(torch.bfloat16))
     s = rnd(392, 128)
@@ -561,9 +589,9 @@ def test_preprocess_patchify_uint8(ops, dtype, H, W, flip):
     ref_img = O.preprocess(img, mean, std, bgr_to_rgb=flip, pad_size_divisor=32, pad_value=0.0)
     ref, (Hp, Wp) = O.patchify(ref_img)
     assert (Hp, Wp) == ops.padded_grid(H, W, 16, 32)
-    cols = ops.preprocess_patchify(img.cuda(), e(3 * Hp * Wp, 768, dtype=dtype), 16, mean, std, bgr_to_rgb=flip, pad_divisor=32, pad_value=0.0)
+    cols = ops.preprocess_patchify(dev(img), e(3 * Hp * Wp, 768, dtype=dtype), 16, mean, std, bgr_to_rgb=flip, pad_divisor=32, pad_value=0.0)
     assert torch.equal(cols.cpu(), ref.to(dtype))
-    cols = ops.preprocess_patchify(img.cuda(), e(3 * Hp * Wp, 768, dtype=dtype), 16, mean, std, bgr_to_rgb=flip, pad_divisor=32, pad_value=-1.5)
+    cols = ops.preprocess_patchify(dev(img), e(3 * Hp * Wp, 768, dtype=dtype), 16, mean, std, bgr_to_rgb=flip, pad_divisor=32, pad_value=-1.5)
     ref2, _ = O.patchify(O.preprocess(img, mean, std, bgr_to_rgb=flip, pad_size_divisor=32, pad_value=-1.5))
     assert torch.equal(cols.cpu(), ref2.to(dtype))
 
@@ -761,14 +789,14 @@ def test_rvsa_pool_and_small_linear(ops, dtype, Hp, Wp):
     ops.small_linear_bwd(pooled, dev(w), dev(dy), dx, dw, db)
     assert rel_err(dx.cpu(), dy @ w) < 1e-5 and rel_err(dw.cpu(), dy.t() @ pr) < 1e-5 and rel_err(db.cpu(), dy.sum(0)) < 1e-5
     base = rnd(T, C, dtype=dtype, seed=4)
-    acc = dev(base, dtype)
+    acc = io(base, dtype)
     ops.rvsa_pool_bwd(dx, avg, acc, B, Hp, Wp, accumulate=True)
     assert rel_err(acc.float().cpu(), base + O.rvsa_pool_bwd(dx.cpu(), ar, B, Hp, Wp)) < TOL[dtype]
     # the fused forms (one launch each way) give the same numbers
     avg2, pooled2, y2 = e(R, C), e(R, C), e(R, 5 * heads)
     ops.rvsa_sampling_fwd(dev(x, dtype), dev(w), dev(b), avg2, pooled2, y2, B, Hp, Wp)
     assert rel_err(avg2.cpu(), ar) < 1e-5 and rel_err(pooled2.cpu(), pr) < 1e-5 and rel_err(y2.cpu(), pr @ w.t() + b) < 1e-5
-    acc2 = dev(base, dtype)
+    acc2 = io(base, dtype)
     ops.rvsa_sampling_bwd(dev(dy), dev(w), avg, acc2, B, Hp, Wp)
     assert rel_err(acc2.float().cpu(), base + O.rvsa_pool_bwd(dy @ w, ar, B, Hp, Wp)) < TOL[dtype]
     dw2, db2 = e(5 * heads, C), e(5 * heads)
@@ -778,7 +806,7 @@ def test_rvsa_pool_and_small_linear(ops, dtype, Hp, Wp):
     rows = [2 * heads, 2 * heads, heads]
     base_w = [rnd(r, C, seed=20 + i) for i, r in enumerate(rows)]
     base_b = [rnd(r, seed=30 + i) for i, r in enumerate(rows)]
-    gw, gb = [dev(t) for t in base_w], [dev(t) for t in base_b]
+    gw, gb = [io(t) for t in base_w], [io(t) for t in base_b]
     ops.small_linear_dw_segments(pooled, dev(dy), gw, gb)
     full_w, full_b, r0 = dy.t() @ pr, dy.sum(0), 0
     for i, r in enumerate(rows):
@@ -797,16 +825,16 @@ def test_batched_small_linear_wgrad_and_deferred_reductions_equal_their_unbatche
     refs = []
     for j in range(njobs):
         x, dy = dev(rnd(R, K, seed=100 + j)), dev(rnd(R, N, seed=200 + j))
-        rw = [dev(rnd(r, K, seed=300 + 7 * j + i)) for i, r in enumerate(rows)]
-        rb = [dev(rnd(r, seed=400 + 7 * j + i)) for i, r in enumerate(rows)]
+        rw = [io(rnd(r, K, seed=300 + 7 * j + i)) for i, r in enumerate(rows)]
+        rb = [io(rnd(r, seed=400 + 7 * j + i)) for i, r in enumerate(rows)]
         ops.small_linear_dw_segments(x, dy, rw, rb)            # the unbatched form, accumulating into the same starting values
         refs.append((rw, rb))
     kept = []
     jobs = []
     for j in range(njobs):
         x, dy = dev(rnd(R, K, seed=100 + j)), dev(rnd(R, N, seed=200 + j))
-        gw = [dev(rnd(r, K, seed=300 + 7 * j + i)) for i, r in enumerate(rows)]
-        gb = [dev(rnd(r, seed=400 + 7 * j + i)) for i, r in enumerate(rows)]
+        gw = [io(rnd(r, K, seed=300 + 7 * j + i)) for i, r in enumerate(rows)]
+        gb = [io(rnd(r, seed=400 + 7 * j + i)) for i, r in enumerate(rows)]
         jobs.append((x, dy, gw, gb))
         kept.append((gw, gb))
     ops.small_linear_dw_segments_flush(jobs)
@@ -820,7 +848,7 @@ def test_batched_small_linear_wgrad_and_deferred_reductions_equal_their_unbatche
         for i in range(nbuf):
             part = dev(rnd(prow, cols, seed=500 + i))
             base = rnd(cols, seed=600 + i)
-            o, r = dev(base), dev(base)
+            o, r = io(base), io(base)
             ops.reduce_rows(part, r, accumulate=acc)
             items.append((part, o, acc))
             outs.append(o)
@@ -836,7 +864,7 @@ def test_batched_small_linear_wgrad_and_deferred_reductions_equal_their_unbatche
         for i in range(nbuf):
             part = rnd(prow, Rt * Ct, seed=700 + i)
             base = rnd(Ct * Rt, seed=800 + i)
-            o = dev(base)
+            o = io(base)
             items.append((dev(part), o, acc, (Rt, Ct)))
             outs.append(o)
             ref = part.sum(0).view(Rt, Ct).t().contiguous().view(-1)
@@ -1020,8 +1048,8 @@ def test_adamw_flat_and_sqnorm(ops):
     lr, b1, b2, eps = 1e-2, 0.9, 0.999, 1e-8
     ref_p = [p[:1024].clone().requires_grad_(True), p[1024:4096].clone().requires_grad_(True), p[4096:].clone().requires_grad_(True)]
     opt = torch.optim.AdamW([{"params": [ref_p[0], ref_p[2]], "weight_decay": 0.05}, {"params": [ref_p[1]], "weight_decay": 0.0}], lr=lr, betas=(b1, b2), eps=eps)
-    dp, dg, dm, dv = dev(p), dev(g), torch.zeros(n, device="cuda"), torch.zeros(n, device="cuda")
-    sq = torch.zeros(1, device="cuda")
+    dp, dg, dm, dv = io(p), dev(g), ARENA.zeros(n), ARENA.zeros(n)
+    sq = ARENA.zeros(1)
     for step in range(1, 4):
         for rp, sl in zip(ref_p, (slice(0, 1024), slice(1024, 4096), slice(4096, n))):
             rp.grad = g[sl].clone()
@@ -1057,13 +1085,13 @@ def test_cu_mask_stream_entry_points(ops):
             seen.append(slots)
         assert not (seen[0] & seen[1])
     # the same GEMM on the whole chip and on a 128-CU stream (other tile height / kernel family by CU count): bit-identical
-    a = torch.randn(6272, 1024, device="cuda").bfloat16()
-    w = torch.randn(1024, 1024, device="cuda").bfloat16()
-    y0 = ops.gemm_nt(a, w, torch.empty(6272, 1024, device="cuda", dtype=torch.bfloat16))
+    a = ARENA.frozen(torch.randn(6272, 1024, device="cuda").bfloat16())
+    w = ARENA.frozen(torch.randn(1024, 1024, device="cuda").bfloat16())
+    y0 = ops.gemm_nt(a, w, e(6272, 1024, dtype=torch.bfloat16))
     st = ops.cu_mask_stream("cuda", ops.cu_mask_words("interleaved", 0))
     st.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(st):
-        y1 = ops.gemm_nt(a, w, torch.empty(6272, 1024, device="cuda", dtype=torch.bfloat16))
+        y1 = ops.gemm_nt(a, w, e(6272, 1024, dtype=torch.bfloat16))
     st.synchronize()
     assert torch.equal(y0, y1)
     h = C.c_void_p()
@@ -1081,8 +1109,8 @@ def test_low_priority_stream_entry_points(ops):
     h = C.c_void_p()
     assert lib.mtp_stream_create_low_priority(C.byref(h)) == 0 and h.value
     st = torch.cuda.ExternalStream(h.value)
-    x = torch.randn(4096, 256, device="cuda")
-    out = torch.zeros(256, device="cuda")
+    x = ARENA.frozen(torch.randn(4096, 256, device="cuda"))
+    out = e(256)
     ready = torch.cuda.Event()
     ready.record()
     with torch.cuda.stream(st):

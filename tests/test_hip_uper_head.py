@@ -9,6 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import guard
 from conftest import rel_err
 from mtp_amd import ops
 import test_uper_head as TU
@@ -18,9 +19,33 @@ pytestmark = pytest.mark.gpu
 F32, BF16 = torch.float32, torch.bfloat16
 
 
+ARENA = None     # the running test's guard.Arena
+
+
+@pytest.fixture(autouse=True)
+def arena(monkeypatch):
+    """the kernel tests' outputs come poisoned and between guards out of a fresh arena, their inputs are frozen, and the wrappers' own workspaces
+    (ops._scratch; the whole-head tests' too) are poisoned and guarded; teardown compares every guard and frozen input bit for bit"""
+    global ARENA
+    ARENA = a = guard.Arena("cuda")
+    monkeypatch.setattr(ops, "_scratch", a.scratch)
+    yield a
+    ARENA = None
+    torch.cuda.synchronize()
+    try:
+        a.check()
+    finally:
+        a.close()
+
+
+def e(*shape, dtype=F32):
+    """an op OUTPUT: NaN-poisoned, between guards"""
+    return ARENA.empty(*shape, dtype=dtype)
+
+
 def rows(x, dtype=F32):
-    """NCHW -> (N*H*W, C) on the device"""
-    return x.permute(0, 2, 3, 1).reshape(-1, x.shape[1]).to("cuda", dtype).contiguous()
+    """NCHW -> (N*H*W, C) on the device: an op INPUT, frozen"""
+    return ARENA.frozen(ARENA.like(x.permute(0, 2, 3, 1).reshape(-1, x.shape[1]), dtype=dtype))
 
 
 def nchw(r, N, H, W):
@@ -35,7 +60,7 @@ BN_GEOM = [(64, 7, 256, 0.5), (64, 14, 256, 0.5), (64, 28, 256, 0.5), (64, 56, 2
 def bn_train_stats(xd, rm, rv):
     """the engine's two-pass statistics: a first mean, then the sums centred on it"""
     C = xd.shape[1]
-    mean, rstd, center = (torch.empty(C, device="cuda") for _ in range(3))
+    mean, rstd, center = (e(C) for _ in range(3))
     ops.bn_finalize(ops.bn_sums(xd), xd.shape[0], None, None, center, rstd)
     ops.bn_finalize(ops.bn_sums(xd, center), xd.shape[0], rm, rv, mean, rstd, center=center)
     return mean, rstd
@@ -55,11 +80,11 @@ def test_batchnorm_relu_train_and_eval_against_torch(N, S, C, offset):
     dy = torch.randn(y_ref.shape, generator=g, dtype=torch.float64)
     y_ref.backward(dy)
     xd, dyd = rows(x), rows(dy)
-    gd, bd, rmd, rvd = gam.cuda(), bet.cuda(), rm.cuda(), rv.cuda()
+    gd, bd, rmd, rvd = ARENA.frozen(ARENA.like(gam)), ARENA.frozen(ARENA.like(bet)), ARENA.like(rm), ARENA.like(rv)     # (the running statistics are updated in place)
     mean, rstd = bn_train_stats(xd, rmd, rvd)
-    y = ops.bn_apply(xd, mean, rstd, gd, bd, torch.empty_like(xd))
+    y = ops.bn_apply(xd, mean, rstd, gd, bd, e(*xd.shape))
     bs = ops.bn_bwd_sums(dyd, xd, mean, rstd, gd, bd)
-    dx = ops.bn_bwd_dx(dyd, xd, mean, rstd, gd, bd, bs, xd.shape[0], torch.empty_like(xd))
+    dx = ops.bn_bwd_dx(dyd, xd, mean, rstd, gd, bd, bs, xd.shape[0], e(*xd.shape))
     assert rel_err(nchw(y, N, S, S), y_ref) < 1e-5 * max(1.0, abs(offset))
     assert rel_err(rmd.cpu(), rm_ref) < 1e-5 and rel_err(rvd.cpu(), rv_ref) < 1e-5
     # dx away from the ReLU's kink: where the float64 pre-activation is within 1e-5 of 0 an f32 forward may take the other side (one such
@@ -69,7 +94,7 @@ def test_batchnorm_relu_train_and_eval_against_torch(N, S, C, offset):
     assert rel_err(nchw(dx, N, S, S) * far, xr.grad * far) < 1e-4 * max(1.0, abs(offset))
     # eval: the running statistics
     ops.bn_finalize(None, 0, rmd, rvd, mean, rstd)
-    ye = ops.bn_apply(xd, mean, rstd, gd, bd, torch.empty(xd.shape, device="cuda", dtype=BF16))
+    ye = ops.bn_apply(xd, mean, rstd, gd, bd, e(*xd.shape, dtype=BF16))
     ye_ref = F.relu(F.batch_norm(x.double(), rmd.cpu().double(), rvd.cpu().double(), gam.double(), bet.double(), False, 0.1, 1e-5))
     assert rel_err(nchw(ye, N, S, S), ye_ref) < 8e-3 * max(1.0, abs(offset) / 10)
 
@@ -87,31 +112,33 @@ def test_resize_bilinear_forward_backward_against_torch(src, dst):
     y_ref = F.interpolate(x, size=dst, mode="bilinear", align_corners=False)
     dy = torch.randn(y_ref.shape, generator=g, dtype=torch.float64)
     y_ref.backward(dy)
-    y = ops.resize_bilinear_fwd(rows(x.detach()), torch.empty(N * dst[0] * dst[1], C, device="cuda"), N, *src, *dst)
+    y = ops.resize_bilinear_fwd(rows(x.detach()), e(N * dst[0] * dst[1], C), N, *src, *dst)
     assert rel_err(nchw(y, N, *dst), y_ref) < 1e-5
-    dx = ops.resize_bilinear_bwd(rows(dy), torch.empty(N * src[0] * src[1], C, device="cuda"), N, *src, *dst)
+    dx = ops.resize_bilinear_bwd(rows(dy), e(N * src[0] * src[1], C), N, *src, *dst)
     assert rel_err(nchw(dx, N, *src), x.grad) < 1e-5
     # accumulate into a column slice of a wider bf16 buffer (the top-down add / the concatenation)
-    wide = torch.zeros(N * dst[0] * dst[1], 3 * C, device="cuda", dtype=BF16)
-    wide[:, C:2 * C] = 1.0
-    ops.resize_bilinear_fwd(rows(x.detach(), BF16), wide[:, C:2 * C], N, *src, *dst, accumulate=True)
-    assert rel_err(nchw(wide[:, C:2 * C].contiguous(), N, *dst), y_ref + 1.0) < 1e-2 and wide[:, :C].abs().max() == 0
+    wide = ARENA.wide(N * dst[0] * dst[1], 3 * C, dtype=BF16)
+    mid = ARENA.cols(wide, C, 2 * C)
+    mid.fill_(1.0)
+    ops.resize_bilinear_fwd(rows(x.detach(), BF16), mid, N, *src, *dst, accumulate=True)
+    assert rel_err(nchw(mid.contiguous(), N, *dst), y_ref + 1.0) < 1e-2
+    ARENA.check()            # the columns on both sides of the slice still hold the poison they were filled with, bit for bit (and the guards)
 
 
 def test_resize_and_bn_backward_are_bit_identical_across_runs():
     N, C, S = 8, 256, 32
     g = torch.Generator().manual_seed(0)
     dy = rows(torch.randn(N, C, 4 * S, 4 * S, generator=g))
-    a = ops.resize_bilinear_bwd(dy, torch.empty(N * S * S, C, device="cuda"), N, S, S, 4 * S, 4 * S)
-    b = ops.resize_bilinear_bwd(dy, torch.empty(N * S * S, C, device="cuda"), N, S, S, 4 * S, 4 * S)
+    a = ops.resize_bilinear_bwd(dy, e(N * S * S, C), N, S, S, 4 * S, 4 * S)
+    b = ops.resize_bilinear_bwd(dy, e(N * S * S, C), N, S, S, 4 * S, 4 * S)
     assert torch.equal(a, b)
     x = rows(torch.randn(N, C, 4 * S, 4 * S, generator=g))
-    gam, bet = torch.ones(C, device="cuda"), torch.zeros(C, device="cuda")
+    gam, bet = ARENA.frozen(torch.ones(C, device="cuda")), ARENA.frozen(torch.zeros(C, device="cuda"))
     mean, rstd = bn_train_stats(x, None, None)
     s1, s2 = ops.bn_bwd_sums(dy, x, mean, rstd, gam, bet), ops.bn_bwd_sums(dy, x, mean, rstd, gam, bet)
     assert torch.equal(s1, s2)
-    d1 = ops.bn_bwd_dx(dy, x, mean, rstd, gam, bet, s1, x.shape[0], torch.empty_like(x))
-    d2 = ops.bn_bwd_dx(dy, x, mean, rstd, gam, bet, s2, x.shape[0], torch.empty_like(x))
+    d1 = ops.bn_bwd_dx(dy, x, mean, rstd, gam, bet, s1, x.shape[0], e(*x.shape))
+    d2 = ops.bn_bwd_dx(dy, x, mean, rstd, gam, bet, s2, x.shape[0], e(*x.shape))
     assert torch.equal(d1, d2) and torch.equal(ops.bn_sums(x), ops.bn_sums(x))
 
 
@@ -123,9 +150,9 @@ def test_adaptive_avg_pool_against_torch(H, S):
     y_ref = F.adaptive_avg_pool2d(x, S)
     dy = torch.randn(y_ref.shape, generator=g, dtype=torch.float64)
     y_ref.backward(dy)
-    y = ops.adaptive_avg_pool_fwd(rows(x.detach()), torch.empty(N * S * S, C, device="cuda"), N, H, H, S)
+    y = ops.adaptive_avg_pool_fwd(rows(x.detach()), e(N * S * S, C), N, H, H, S)
     assert rel_err(nchw(y, N, S, S), y_ref) < 1e-5
-    dx = ops.adaptive_avg_pool_bwd(rows(dy), torch.zeros(N * H * H, C, device="cuda"), N, H, H, S)
+    dx = ops.adaptive_avg_pool_bwd(rows(dy), e(N * H * H, C), N, H, H, S)      # (accumulate=False: every pixel lies in a bin and is overwritten)
     assert rel_err(nchw(dx, N, H, H), x.grad) < 1e-5
 
 
@@ -142,7 +169,9 @@ def test_seg_loss_against_torch(N, h, K, label_dtype, ignored):
     Kp = ops.pad8(K)
     lr = torch.zeros(N * h * h, Kp, device="cuda")
     lr[:, :K] = rows(logits.detach())
-    loss, dl = ops.seg_ce(lr, K, N, h, h, lab.to("cuda", label_dtype), 255, 0.7)
+    labd = lab.to("cuda", label_dtype)
+    ARENA.frozen(lr, labd)
+    loss, dl = ops.seg_ce(lr, K, N, h, h, labd, 255, 0.7)
     assert dl.shape == (N * h * h, Kp)
     if ignored == 1.0:
         assert loss.item() == 0.0 and dl.abs().max().item() == 0.0
