@@ -284,6 +284,30 @@ int mtp_full_attn_bwd(const void* qkv, const void* o, const void* dout, const fl
                       const float* rel_h, const float* rel_w, float* drel_part, float* workspace,
                       int64_t B, int64_t Hp, int64_t Wp, int64_t heads, int64_t hd, float scale, mtp_stream_t stream);
 
+/* Which kernel family mtp_full_attn_fwd / _bwd (backward != 0) resp. mtp_rvsa_attn_fwd / _bwd run for this dtype and token grid: the value of the
+ * very decision the entry points launch by, no launch, no device needed.  MTP_ERR_ARG for a dtype other than f32 / bf16, Hp or Wp <= 0 (< 7 for
+ * RVSA) or heads <= 0; MTP_ATTN_KERNEL_NONE where the entry point would return MTP_ERR_UNSUPPORTED. */
+enum {
+    MTP_ATTN_KERNEL_NONE = 0,
+    MTP_FULL_FWD_V3 = 1,          /* row-aligned MFMA kernels, grids <= 16 x 16 */
+    MTP_FULL_FWD_MFMA1 = 2,       /* one workgroup per (image, head), <= 256 tokens */
+    MTP_FULL_FWD_FLASH128 = 3,    /* flash, 128-key blocks (sides <= 32) */
+    MTP_FULL_FWD_FLASH256 = 4,    /* flash, 256-key blocks (a side of 33 .. 64) */
+    MTP_FULL_FWD_GENERIC = 5,     /* f32-math kernel */
+    MTP_FULL_BWD_V3 = 1,
+    MTP_FULL_BWD_MFMA1 = 2,       /* the a / b pair, one workgroup per (image, head) */
+    MTP_FULL_BWD_FLASH = 3,
+    MTP_FULL_BWD_THREE_PASS = 4,  /* f32 math, > 256 tokens, needs the workspace */
+    MTP_FULL_BWD_SINGLE_WG = 5,   /* f32 math, <= 256 tokens */
+    MTP_RVSA_FWD_GENERIC = 1,
+    MTP_RVSA_FWD_MFMA = 2,
+    MTP_RVSA_BWD_GENERIC = 1,
+    MTP_RVSA_BWD_MFMA_DENSE = 2,  /* k / v gradients scattered by a dense-product kernel */
+    MTP_RVSA_BWD_MFMA_ATOMIC = 3  /* ... by f32 atomics inside the backward kernel */
+};
+int mtp_full_attn_kernel(int dtype, int64_t Hp, int64_t Wp, int backward);
+int mtp_rvsa_attn_kernel(int dtype, int64_t Hp, int64_t Wp, int64_t heads, int backward);
+
 /* RVSA sampling heads, stage 1 (VIT:347 zero pad, AvgPool2d(7,7), LeakyReLU): x (T,C) ACT -> avg, pooled (B*nh*nw, C) f32 */
 int mtp_rvsa_pool_fwd(const void* x, int dtype, float* avg, float* pooled, int64_t B, int64_t Hp, int64_t Wp, int64_t C, mtp_stream_t stream);
 /* dx (T,C) ACT += / = dpooled * leaky'(avg) / 49 broadcast over the window */

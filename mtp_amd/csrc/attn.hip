@@ -826,19 +826,67 @@ RvsaGeom make_geom(int64_t Hp, int64_t Wp, int64_t heads) {
     return g;
 }
 
+// ---- the dispatch: which kernel family takes (dtype, grid).  The entry points below launch what these name; mtp_full_attn_kernel /
+// mtp_rvsa_attn_kernel report the same value (the tests assert it per case).  bf16 I/O takes the MFMA families where one fits; f32 I/O
+// (parity mode) and the remaining grids run the f32-math kernels of this file.
+size_t full_fwd_generic_lds(int64_t Hp, int64_t Wp) { return sizeof(float) * (size_t)(2 * KT * HD + (Hp + Wp) * 256 + KT * 256); }
+size_t full_bwd3_lds_q(int64_t Hp, int64_t Wp) { return sizeof(float) * (size_t)(2 * (Hp + Wp) * 256 + 2 * KT * HD); }
+size_t full_bwd1_lds(int64_t Hp, int64_t Wp) { return sizeof(float) * (size_t)(2 * (Hp + Wp) * 256 + 512 + 2 * KT * HD); }
+
+int full_fwd_family(int dtype, int64_t Hp, int64_t Wp) {
+    if (dtype == MTP_BF16 && mtp_use_mfma_attn()) {
+        if (mtp_full_v3_fits(Hp, Wp)) return MTP_FULL_FWD_V3;
+        if (mtp_full_mfma1_fits(Hp, Wp, false)) return MTP_FULL_FWD_MFMA1;
+        const int keys = mtp_full_fwd_flash_keys(Hp, Wp);
+        if (keys) return keys == 256 ? MTP_FULL_FWD_FLASH256 : MTP_FULL_FWD_FLASH128;
+    }   // larger token grids fall through to the generic kernel
+    return full_fwd_generic_lds(Hp, Wp) <= 160 * 1024 ? MTP_FULL_FWD_GENERIC : MTP_ATTN_KERNEL_NONE;
+}
+
+int full_bwd_family(int dtype, int64_t Hp, int64_t Wp) {
+    if (dtype == MTP_BF16 && mtp_use_mfma_attn()) {
+        if (mtp_full_v3_fits(Hp, Wp)) return MTP_FULL_BWD_V3;
+        if (mtp_full_mfma1_fits(Hp, Wp, true)) return MTP_FULL_BWD_MFMA1;
+        if (mtp_full_bwd_flash_fits(Hp, Wp)) return MTP_FULL_BWD_FLASH;
+    }
+    if (Hp * Wp > 256)   // multi-workgroup three-pass backward (448^2 / 512^2 inputs); needs the caller's workspace
+        return full_bwd3_lds_q(Hp, Wp) <= 160 * 1024 ? MTP_FULL_BWD_THREE_PASS : MTP_ATTN_KERNEL_NONE;
+    if ((2 * Hp - 1) + (2 * Wp - 1) > 4 * MAXR) return MTP_ATTN_KERNEL_NONE;   // single-workgroup backward (224^2..256^2 inputs)
+    return full_bwd1_lds(Hp, Wp) <= 160 * 1024 ? MTP_FULL_BWD_SINGLE_WG : MTP_ATTN_KERNEL_NONE;
+}
+
+int rvsa_fwd_family(int dtype) { return dtype == MTP_BF16 && mtp_use_mfma_attn() ? MTP_RVSA_FWD_MFMA : MTP_RVSA_FWD_GENERIC; }
+
+int rvsa_bwd_family(int dtype, int64_t Hp, int64_t Wp, int64_t heads) {
+    if (!(dtype == MTP_BF16 && mtp_use_mfma_attn())) return MTP_RVSA_BWD_GENERIC;
+    return mtp_rvsa_bwd_mfma_scatter_mode(Hp, Wp, heads) == 4 ? MTP_RVSA_BWD_MFMA_DENSE : MTP_RVSA_BWD_MFMA_ATOMIC;
+}
+
 }  // namespace
+
+extern "C" int mtp_full_attn_kernel(int dtype, int64_t Hp, int64_t Wp, int backward) {
+    if ((dtype != MTP_F32 && dtype != MTP_BF16) || Hp <= 0 || Wp <= 0) return MTP_ERR_ARG;
+    return backward ? full_bwd_family(dtype, Hp, Wp) : full_fwd_family(dtype, Hp, Wp);
+}
+
+extern "C" int mtp_rvsa_attn_kernel(int dtype, int64_t Hp, int64_t Wp, int64_t heads, int backward) {
+    if ((dtype != MTP_F32 && dtype != MTP_BF16) || Hp < 7 || Wp < 7 || heads <= 0) return MTP_ERR_ARG;
+    return backward ? rvsa_bwd_family(dtype, Hp, Wp, heads) : rvsa_fwd_family(dtype);
+}
 
 extern "C" int mtp_full_attn_fwd(const void* qkv, void* o, float* lse, int dtype, const float* rel_h, const float* rel_w,
                                  int64_t B, int64_t Hp, int64_t Wp, int64_t heads, int64_t hd, float scale, mtp_stream_t stream) {
     if (!qkv || !o || !lse || !rel_h || !rel_w || B <= 0 || Hp <= 0 || Wp <= 0 || heads <= 0) return MTP_ERR_ARG;
     if (hd != HD) return MTP_ERR_UNSUPPORTED;
-    if (dtype == MTP_BF16 && mtp_use_mfma_attn()) {
-        const int rc = mtp_full_fwd_mfma_launch(qkv, o, lse, rel_h, rel_w, B, Hp, Wp, heads, scale, (hipStream_t)stream);
-        if (rc != MTP_ERR_UNSUPPORTED) return rc;   // larger token grids fall through to the generic kernel
+    switch (full_fwd_family(dtype, Hp, Wp)) {
+        case MTP_FULL_FWD_V3: return mtp_full_v3_fwd_launch(qkv, o, lse, rel_h, rel_w, B, Hp, Wp, heads, scale, (hipStream_t)stream);
+        case MTP_FULL_FWD_MFMA1: case MTP_FULL_FWD_FLASH128: case MTP_FULL_FWD_FLASH256:
+            return mtp_full_fwd_mfma_launch(qkv, o, lse, rel_h, rel_w, B, Hp, Wp, heads, scale, (hipStream_t)stream);
+        case MTP_FULL_FWD_GENERIC: break;
+        default: return MTP_ERR_UNSUPPORTED;
     }
     const int N = (int)(Hp * Wp);
-    const size_t lds = sizeof(float) * (size_t)(2 * KT * HD + (Hp + Wp) * 256 + KT * 256);
-    if (lds > 160 * 1024) return MTP_ERR_UNSUPPORTED;
+    const size_t lds = full_fwd_generic_lds(Hp, Wp);
     dim3 grid((unsigned)(B * heads), (unsigned)((N + 255) / 256)), block(256);
     hipStream_t s = (hipStream_t)stream;
     if (dtype == MTP_BF16) {
@@ -859,21 +907,23 @@ extern "C" int64_t mtp_full_attn_bwd_workspace_floats(int64_t B, int64_t Hp, int
 extern "C" int mtp_full_attn_bwd(const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv, int dtype,
                                  const float* rel_h, const float* rel_w, float* drel_part, float* workspace,
                                  int64_t B, int64_t Hp, int64_t Wp, int64_t heads, int64_t hd, float scale, mtp_stream_t stream) {
-    if (!qkv || !o || !dout || !lse || !dqkv || !rel_h || !rel_w || !drel_part || B <= 0 || heads <= 0) return MTP_ERR_ARG;
+    if (!qkv || !o || !dout || !lse || !dqkv || !rel_h || !rel_w || !drel_part || B <= 0 || Hp <= 0 || Wp <= 0 || heads <= 0) return MTP_ERR_ARG;
     if (hd != HD) return MTP_ERR_UNSUPPORTED;
-    if (dtype == MTP_BF16 && mtp_use_mfma_attn()) {
-        int rc = mtp_full_bwd_mfma_launch(qkv, o, dout, lse, dqkv, rel_h, rel_w, drel_part, B, Hp, Wp, heads, scale, (hipStream_t)stream);
-        if (rc != MTP_ERR_UNSUPPORTED) return rc;
-        rc = mtp_full_bwd_flash_launch(qkv, o, dout, lse, dqkv, rel_h, rel_w, drel_part, workspace, B, Hp, Wp, heads, scale, (hipStream_t)stream);
-        if (rc != MTP_ERR_UNSUPPORTED) return rc;
+    const int family = full_bwd_family(dtype, Hp, Wp);
+    switch (family) {
+        case MTP_FULL_BWD_V3: return mtp_full_v3_bwd_launch(qkv, o, dout, lse, dqkv, rel_h, rel_w, drel_part, B, Hp, Wp, heads, scale, (hipStream_t)stream);
+        case MTP_FULL_BWD_MFMA1: return mtp_full_bwd_mfma_launch(qkv, o, dout, lse, dqkv, rel_h, rel_w, drel_part, B, Hp, Wp, heads, scale, (hipStream_t)stream);
+        case MTP_FULL_BWD_FLASH:
+            return mtp_full_bwd_flash_launch(qkv, o, dout, lse, dqkv, rel_h, rel_w, drel_part, workspace, B, Hp, Wp, heads, scale, (hipStream_t)stream);
+        case MTP_FULL_BWD_THREE_PASS: case MTP_FULL_BWD_SINGLE_WG: break;
+        default: return MTP_ERR_UNSUPPORTED;
     }
     const int N = (int)(Hp * Wp);
-    if (N > 256) {   // multi-workgroup three-pass backward (448^2 / 512^2 inputs); needs the caller's workspace
+    if (family == MTP_FULL_BWD_THREE_PASS) {
         if (!workspace) return MTP_ERR_ARG;
         const int HW = (int)(Hp + Wp), RT = (int)(2 * Hp - 1 + 2 * Wp - 1);
-        const size_t lds_q = sizeof(float) * (size_t)(2 * HW * 256 + 2 * KT * HD);
+        const size_t lds_q = full_bwd3_lds_q(Hp, Wp);
         const size_t lds_k = sizeof(float) * (size_t)(2 * KT * HD + HW * KT + 2 * KT);
-        if (lds_q > 160 * 1024) return MTP_ERR_UNSUPPORTED;
         hipStream_t s = (hipStream_t)stream;
         dim3 gq((unsigned)(B * heads), (unsigned)((N + 255) / 256)), gt((unsigned)(B * heads), (unsigned)((RT + 3) / 4)), block(256);
         if (dtype == MTP_BF16) {
@@ -893,9 +943,7 @@ extern "C" int mtp_full_attn_bwd(const void* qkv, const void* o, const void* dou
         }
         return mtp_launch_status();
     }
-    if ((2 * Hp - 1) + (2 * Wp - 1) > 4 * MAXR) return MTP_ERR_UNSUPPORTED;   // single-workgroup backward (224^2..256^2 inputs)
-    const size_t lds = sizeof(float) * (size_t)(2 * (Hp + Wp) * 256 + 512 + 2 * KT * HD);
-    if (lds > 160 * 1024) return MTP_ERR_UNSUPPORTED;
+    const size_t lds = full_bwd1_lds(Hp, Wp);
     dim3 grid((unsigned)(B * heads)), block(256);
     hipStream_t s = (hipStream_t)stream;
     if (dtype == MTP_BF16) {
@@ -918,7 +966,7 @@ extern "C" int mtp_rvsa_attn_fwd(const void* qkv, const float* samp, void* o, fl
     const RvsaGeom g = make_geom(Hp, Wp, heads);
     dim3 grid((unsigned)(B * g.nh * g.nw * heads)), block(64);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == MTP_BF16 && mtp_use_mfma_attn())
+    if (rvsa_fwd_family(dtype) == MTP_RVSA_FWD_MFMA)
         return mtp_rvsa_fwd_mfma_launch(qkv, samp, o, lse, rel_h, rel_w, bias_table, B, Hp, Wp, heads, scale, s);
     if (dtype == MTP_BF16)
         hipLaunchKernelGGL((rvsa_attn_fwd_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)qkv, samp, (bf16_t*)o, lse, rel_h, rel_w, bias_table, g, scale);
@@ -937,7 +985,8 @@ extern "C" int mtp_rvsa_attn_bwd(const void* qkv, const float* samp, const void*
     const RvsaGeom g = make_geom(Hp, Wp, heads);
     const int64_t Ttok = B * Hp * Wp, C = heads * HD;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == MTP_BF16 && mtp_use_mfma_attn() && mtp_rvsa_bwd_mfma_scatter_mode(Hp, Wp, heads) == 4)     // dense-product scatter: dqkv's k / v
+    const int family = rvsa_bwd_family(dtype, Hp, Wp, heads);
+    if (family == MTP_RVSA_BWD_MFMA_DENSE)     // dense-product scatter: dqkv's k / v
         return mtp_rvsa_bwd_mfma_launch(qkv, samp, o, dout, lse, dqkv, dkv_f32, dsamp, rel_part, tab_part, rel_h, rel_w, bias_table, B, Hp, Wp, heads, scale, s);   // parts are written once, no scratch passes
     hipError_t e = hipMemsetAsync(dkv_f32, 0, sizeof(float) * (size_t)(Ttok * 2 * C), s);
     if (e != hipSuccess) return (int)e;
@@ -945,7 +994,7 @@ extern "C" int mtp_rvsa_attn_bwd(const void* qkv, const float* samp, const void*
     dim3 grid((unsigned)(B * g.nh * g.nw * heads)), block(64);
     int64_t cb = (Ttok * 2 * C / 4 + 255) / 256;
     dim3 cgrid((unsigned)(cb > 8192 ? 8192 : cb)), cblock(256);
-    if (dtype == MTP_BF16 && mtp_use_mfma_attn()) {
+    if (family == MTP_RVSA_BWD_MFMA_ATOMIC) {
         const int rc = mtp_rvsa_bwd_mfma_launch(qkv, samp, o, dout, lse, dqkv, dkv_f32, dsamp, rel_part, tab_part, rel_h, rel_w, bias_table, B, Hp, Wp, heads, scale, s);
         if (rc) return rc;
         hipLaunchKernelGGL((dkv_convert_kernel<bf16_t>), cgrid, cblock, 0, s, dkv_f32, (bf16_t*)dqkv, Ttok, (int)C);

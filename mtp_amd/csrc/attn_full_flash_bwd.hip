@@ -392,29 +392,44 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(const bf16_t* __rest
 
 }  // namespace
 
+static void flash_geom(int64_t Hp, int64_t Wp, int64_t heads, FlashGeom& g) {
+    g.N = (int)(Hp * Wp); g.Hp = (int)Hp; g.Wp = (int)Wp; g.heads = (int)heads;
+    g.HW = g.Hp + g.Wp; g.HWP = g.HW | 1;
+    g.RH = 2 * g.Hp - 1; g.RW = 2 * g.Wp - 1;
+    g.WT = (g.Wp + 15) / 16;
+}
+// LDS of the dq kernel with key blocks of kb keys (bytes)
+static size_t flash_lds_q(const FlashGeom& g, int kb) {
+    return 2 * (size_t)kb * 128 + (size_t)(1 + g.WT) * (kb / 32) * 64 * 16 + 2 * (size_t)64 * g.HWP * 4 + 4 * 64 * QTP + kb * 4 + 64 * 4;
+}
+// key block of the dq kernel: 64 keys when that brings its LDS under half a CU's (two workgroups = 8 waves per CU; 28 x 28: 70 KiB)
+// and the indicator rows still fit one MFMA tile (64 / Wp + 2 <= 16 always holds for Wp >= 10)
+static bool flash_small(const FlashGeom& g) { return flash_lds_q(g, 64) <= 80 * 1024; }
+
+bool mtp_full_bwd_flash_fits(int64_t Hp, int64_t Wp) {
+    // (<= 256 tokens: measured at 14 x 14, B = 64: 579 us vs 590 us for the one-workgroup-per-(image, head) kernels -- 196 = 3 x 64 + 4
+    //  wastes a quarter of the query workgroups; not worth a second code path)
+    if (Hp < 1 || Wp < 1 || Hp * Wp <= 256 || Hp > 64 || Wp > 64 || Wp < 10) return false;
+    FlashGeom g;
+    flash_geom(Hp, Wp, 1, g);
+    return flash_small(g) || flash_lds_q(g, 128) <= 160 * 1024;
+}
+
 // workspace (f32, mtp_full_attn_bwd_workspace_floats): bias rows (B*heads, N, Hp + Wp) | delta (B*heads, N)
 int mtp_full_bwd_flash_launch(const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv, const float* rel_h, const float* rel_w,
                               float* drel_part, float* workspace, int64_t B, int64_t Hp, int64_t Wp, int64_t heads, float scale, hipStream_t s) {
     const int64_t N = Hp * Wp;
-    // (<= 256 tokens: measured at 14 x 14, B = 64: 579 us vs 590 us for the one-workgroup-per-(image, head) kernels -- 196 = 3 x 64 + 4
-    //  wastes a quarter of the query workgroups; not worth a second code path)
-    if (N <= 256 || Hp > 64 || Wp > 64 || Wp < 10) return MTP_ERR_UNSUPPORTED;
+    if (!mtp_full_bwd_flash_fits(Hp, Wp)) return MTP_ERR_UNSUPPORTED;
     if (!workspace) return MTP_ERR_ARG;
     FlashGeom g;
-    g.N = (int)N; g.Hp = (int)Hp; g.Wp = (int)Wp; g.heads = (int)heads;
-    g.HW = g.Hp + g.Wp; g.HWP = g.HW | 1;
-    g.RH = 2 * g.Hp - 1; g.RW = 2 * g.Wp - 1;
-    g.WT = (g.Wp + 15) / 16;
+    flash_geom(Hp, Wp, heads, g);
     float* bias = workspace;
     float* delta = workspace + B * heads * N * g.HW;
     hipError_t e = hipMemsetAsync(drel_part, 0, sizeof(float) * (size_t)(B * heads) * (size_t)(g.RH + g.RW) * HD, s);
     if (e != hipSuccess) return (int)e;
-    const auto lds_q = [&](int kb) { return 2 * (size_t)kb * 128 + (size_t)(1 + g.WT) * (kb / 32) * 64 * 16 + 2 * (size_t)64 * g.HWP * 4 + 4 * 64 * QTP + kb * 4 + 64 * 4; };
+    const auto lds_q = [&](int kb) { return flash_lds_q(g, kb); };
     const size_t lds_k = 2 * (size_t)64 * 128 + (size_t)64 * (g.Wp | 1) * 4 + 64 * 9 * 4 + 2 * 64 * 4;
-    // key block of the dq kernel: 64 keys when that brings its LDS under half a CU's (two workgroups = 8 waves per CU; 28 x 28: 70 KiB)
-    // and the indicator rows still fit one MFMA tile (64 / Wp + 2 <= 16 always holds for Wp >= 10)
-    const bool small = lds_q(64) <= 80 * 1024;
-    if (!small && lds_q(128) > 160 * 1024) return MTP_ERR_UNSUPPORTED;
+    const bool small = flash_small(g);
     const dim3 grid((unsigned)(B * heads), (unsigned)((N + 63) / 64)), block(256);
     (void)hipFuncSetAttribute((const void*)flash_bwd_dq_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q(64));
     (void)hipFuncSetAttribute((const void*)flash_bwd_dq_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q(128));

@@ -640,16 +640,32 @@ bool make_fgeom(int64_t Hp, int64_t Wp, int64_t heads, FGeom& g) {
 
 }  // namespace
 
+// LDS of the two single-workgroup backward kernels (bytes)
+static size_t mfma1_lds_a(const FGeom& g, int nw) {
+    return 2 * (size_t)g.NP2 * 128 + 2 * (size_t)nw * 64 * 16 * 4 + (size_t)nw * 64 * QTP + (size_t)g.NP2 * 4 + 2 * (size_t)g.KK * 64 * 16;
+}
+static size_t mfma1_lds_b(const FGeom& g) { return 2 * (size_t)64 * g.TPV + (size_t)64 * g.NP * 4 + 2 * (size_t)g.NP * 4 + (size_t)g.NP2 * 4; }
+
+bool mtp_full_mfma1_fits(int64_t Hp, int64_t Wp, bool backward) {
+    FGeom g;
+    if (Hp < 1 || Wp < 1 || !make_fgeom(Hp, Wp, 1, g)) return false;
+    return !backward || (mfma1_lds_a(g, 4) <= 160 * 1024 && mfma1_lds_b(g) <= 160 * 1024);
+}
+
+int mtp_full_fwd_flash_keys(int64_t Hp, int64_t Wp) {
+    if (Hp < 1 || Wp < 1 || Hp * Wp <= 256 || Hp > 64 || Wp > 64) return 0;
+    return (Hp > 32 || Wp > 32) ? 256 : 128;          // tables of up to 127 rows: 8 row tiles each
+}
+
 int mtp_full_fwd_mfma_launch(const void* qkv, void* o, float* lse, const float* rel_h, const float* rel_w,
                              int64_t B, int64_t Hp, int64_t Wp, int64_t heads, float scale, hipStream_t s) {
-    if (mtp_full_v3_fits(Hp, Wp)) return mtp_full_v3_fwd_launch(qkv, o, lse, rel_h, rel_w, B, Hp, Wp, heads, scale, s);
     FGeom g;
-    if (!make_fgeom(Hp, Wp, heads, g)) {
+    if (!mtp_full_mfma1_fits(Hp, Wp, false)) {
         const int64_t N = Hp * Wp;
-        if (N <= 256 || Hp > 64 || Wp > 64) return MTP_ERR_UNSUPPORTED;
-        const bool big = Hp > 32 || Wp > 32;          // tables of up to 127 rows: 8 row tiles each
+        const int keys = mtp_full_fwd_flash_keys(Hp, Wp);
+        if (!keys) return MTP_ERR_UNSUPPORTED;
         const dim3 grid((unsigned)(B * heads), (unsigned)((N + 63) / 64));
-        if (big) {
+        if (keys == 256) {
             constexpr int KBLK = 256;
             const size_t lds = 2 * (size_t)KBLK * 128 + (size_t)4 * 32 * 8 * 16 * 4 + KBLK * 4;
             (void)hipFuncSetAttribute((const void*)full_fwd_flash_mfma_kernel<8, KBLK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -663,6 +679,7 @@ int mtp_full_fwd_mfma_launch(const void* qkv, void* o, float* lse, const float* 
         }
         return mtp_launch_status();
     }
+    make_fgeom(Hp, Wp, heads, g);
     const size_t lds = (size_t)g.NT * 16 * 128 + (size_t)64 * g.TPV + 4 * 64 * 16 * 4 + (size_t)g.NP2 * 4;
     (void)hipFuncSetAttribute((const void*)full_fwd_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(full_fwd_mfma_kernel, dim3((unsigned)(B * heads)), dim3(256), lds, s, (const bf16_t*)qkv, (bf16_t*)o, lse, rel_h, rel_w, g, scale);
@@ -671,14 +688,13 @@ int mtp_full_fwd_mfma_launch(const void* qkv, void* o, float* lse, const float* 
 
 int mtp_full_bwd_mfma_launch(const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv, const float* rel_h, const float* rel_w,
                              float* drel_part, int64_t B, int64_t Hp, int64_t Wp, int64_t heads, float scale, hipStream_t s) {
-    if (mtp_full_v3_fits(Hp, Wp)) return mtp_full_v3_bwd_launch(qkv, o, dout, lse, dqkv, rel_h, rel_w, drel_part, B, Hp, Wp, heads, scale, s);
     FGeom g;
-    if (!make_fgeom(Hp, Wp, heads, g)) return MTP_ERR_UNSUPPORTED;
+    if (!mtp_full_mfma1_fits(Hp, Wp, true)) return MTP_ERR_UNSUPPORTED;
+    make_fgeom(Hp, Wp, heads, g);
     hipError_t e = hipMemsetAsync(drel_part, 0, sizeof(float) * (size_t)(B * heads) * (size_t)(g.RH + g.RW) * HD, s);
     if (e != hipSuccess) return (int)e;
-    const auto lds_a = [&](int nw) { return 2 * (size_t)g.NP2 * 128 + 2 * (size_t)nw * 64 * 16 * 4 + (size_t)nw * 64 * QTP + (size_t)g.NP2 * 4 + 2 * (size_t)g.KK * 64 * 16; };
-    const size_t lds_b = 2 * (size_t)64 * g.TPV + (size_t)64 * g.NP * 4 + 2 * (size_t)g.NP * 4 + (size_t)g.NP2 * 4;
-    if (lds_a(4) > 160 * 1024 || lds_b > 160 * 1024) return MTP_ERR_UNSUPPORTED;
+    const auto lds_a = [&](int nw) { return mfma1_lds_a(g, nw); };
+    const size_t lds_b = mfma1_lds_b(g);
     (void)hipFuncSetAttribute((const void*)full_bwd_a_mfma_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_a(8) <= 160 * 1024 ? lds_a(8) : lds_a(4)));
     (void)hipFuncSetAttribute((const void*)full_bwd_a_mfma_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a(4));
     (void)hipFuncSetAttribute((const void*)full_bwd_b_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);

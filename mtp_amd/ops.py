@@ -664,6 +664,29 @@ def full_attn_bwd(qkv, o, dout, lse, dqkv, rel_h, rel_w, drel_h, drel_w, B, Hp, 
     return dqkv
 
 
+# kernel families, as include/mtp_hip.h names them (0 = none: the entry point would refuse the grid as unsupported)
+FULL_FWD = {"v3": 1, "mfma1": 2, "flash128": 3, "flash256": 4, "generic": 5}
+FULL_BWD = {"v3": 1, "mfma1": 2, "flash": 3, "three_pass": 4, "single_wg": 5}
+RVSA_FWD = {"generic": 1, "mfma": 2}
+RVSA_BWD = {"generic": 1, "mfma_dense": 2, "mfma_atomic": 3}
+
+
+def full_attn_kernel(dtype, Hp, Wp, backward=False):
+    """the kernel family full_attn_fwd / full_attn_bwd run for this dtype and grid (a FULL_FWD / FULL_BWD value, 0 = unsupported); no launch, no device"""
+    rc = lib().mtp_full_attn_kernel(_DT[dtype], Hp, Wp, int(backward))
+    if rc < 0:
+        check(rc, "mtp_full_attn_kernel")
+    return rc
+
+
+def rvsa_attn_kernel(dtype, Hp, Wp, heads, backward=False):
+    """the kernel family rvsa_attn_fwd / rvsa_attn_bwd run for this dtype and grid (a RVSA_FWD / RVSA_BWD value); no launch, no device"""
+    rc = lib().mtp_rvsa_attn_kernel(_DT[dtype], Hp, Wp, heads, int(backward))
+    if rc < 0:
+        check(rc, "mtp_rvsa_attn_kernel")
+    return rc
+
+
 def rvsa_windows(Hp, Wp):
     nh = (Hp + (7 - Hp % 7) % 7) // 7
     nw = (Wp + (7 - Wp % 7) % 7) // 7
