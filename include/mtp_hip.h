@@ -45,6 +45,38 @@ typedef enum {
     MTP_EPI_MUL = 5           /* C = acc * aux                                                            */
 } mtp_epilogue;
 
+/* mtp_gemm_args.variant: flags that force A/B choices of the GEMM entry points.  All variants of one problem give bit-identical results.
+ * The numeric values are ABI (A/B libraries and recorded profiles refer to them).  NT = mtp_gemm_nt, TN = mtp_gemm_tn, TNG = mtp_gemm_tn_grouped;
+ * a flag of another entry point is ignored.  Bits 3, 7 and 11-14 selected kernels that are gone and are ignored. */
+typedef enum {
+    MTP_GEMM_NT_REG_STAGED = 1,          /* NT: the 128-wide kernel that stages its tiles through registers (also taken for ragged K) */
+    MTP_GEMM_ORDER_SHIFT = 1,            /* NT, TN: tile order field, bits 1-2; 0 = picked per problem */
+    MTP_GEMM_ORDER_PLAIN = 1 << 1,       /*   tiles in blockIdx order: no XCD remap, no grouping */
+    MTP_GEMM_ORDER_GROUPED = 2 << 1,     /*   NT: panels of 8 tile rows;  TN: M fastest */
+    MTP_GEMM_ORDER_ROW_MAJOR = 3 << 1,   /*   NT: row-major with XCD remap;  TN: N fastest */
+    MTP_GEMM_ORDER_MASK = 3 << 1,
+    MTP_GEMM_TNG_PLAIN_ORDER = 1 << 1,   /* TNG (read from args[0]): tiles in blockIdx order; the same bit as MTP_GEMM_ORDER_PLAIN */
+    MTP_GEMM_TN_REG_TRANSPOSE = 1 << 4,  /* TN: the register-transposing kernels instead of the transpose-read kernel */
+    MTP_GEMM_NT_SB8 = 1 << 5,            /* NT: force the 256 x 128 8-wave tile of the 128-wide family */
+    MTP_GEMM_NT_NO_SB8 = 1 << 6,         /* NT: forbid it */
+    MTP_GEMM_NT_P8 = 1 << 8,             /* NT: force the 8-phase pipelined kernel (when the problem fits), tile height picked per problem */
+    MTP_GEMM_NT_P8_224 = 2 << 8,         /*   ... with 224 x 256 tiles */
+    MTP_GEMM_NT_P8_256 = 3 << 8,         /*   ... with 256 x 256 tiles */
+    MTP_GEMM_NT_P8_MASK = 3 << 8,
+    MTP_GEMM_NT_NO_P8 = 1 << 10,         /* NT: forbid the 8-phase kernel and the strip kernel: the 128-wide family runs */
+    MTP_GEMM_NT_PERSIST = 1 << 15,       /* NT: force the persistent-tile form of the 8-phase kernel */
+    MTP_GEMM_TN_TR_FULL_ONLY = 1 << 15,  /* TN: the transpose-read kernel on complete tiles only, no edge tiles (bit 15 is overloaded: NT reads it as PERSIST) */
+    MTP_GEMM_NT_NO_PERSIST = 1 << 16,    /* NT: forbid the persistent-tile form */
+    MTP_GEMM_NT_STRIP = 1 << 17,         /* NT: force the strip kernel (when the problem fits and no 8-phase form is forced) */
+    MTP_GEMM_NT_NO_STRIP = 1 << 18,      /* NT: forbid it */
+    MTP_GEMM_TNG_PLAIN_PHASES = 1 << 19, /* TNG (read from args[0]): the plain phases instead of the read-ahead phases */
+    MTP_GEMM_STORE_SHIFT = 20,           /* NT: store policy of the 8-phase kernel's epilogue, bits 20-21; 0 = by epilogue (sc1 for the f32 residual form, else nt) */
+    MTP_GEMM_STORE_NT = 1 << 20,         /*   nontemporal stores */
+    MTP_GEMM_STORE_SC1 = 2 << 20,        /*   sc1 write-through stores */
+    MTP_GEMM_STORE_PLAIN = 3 << 20,      /*   plain stores */
+    MTP_GEMM_STORE_MASK = 3 << 20
+} mtp_gemm_variant;
+
 typedef struct {
     const void* A;      /* NT: (M, K) row-major, lda.   TN: (Kc, M) row-major, lda                         */
     const void* B;      /* NT: (N, K) row-major, ldb.   TN: (Kc, N) row-major, ldb                         */
@@ -66,15 +98,7 @@ typedef struct {
                          * summed into C by the callee (deterministic); NULL = f32 atomicAdd into zeroed C  */
     int64_t aux_ld;
     int split_k;        /* TN only: >1 = split the contraction over gridDim.y                               */
-    int variant;        /* 0 = default kernels and heuristics; other values force A/B choices (debug / tests): bit0 NT register-
-                         * staged loads; bits1-2 tile order (1 plain, 2 grouped / M-fastest, 3 row-major); bit3 TN single-stage;
-                         * bit4 TN register-transposing; bit5 / bit6 force / forbid the 256x128 8-wave NT tile; bits8-9 the 8-wave
-                         * pipelined NT kernel (1 = tile height picked per problem, 2 = 224 x 256 tiles, 3 = 256 x 256 tiles), bit10
-                         * forbids it; bit15 / bit16 force / forbid its persistent-tile form; bits20-21 store policy of its epilogue
-                         * (0 = by epilogue: nt, sc1 for the f32 residual form; 1 = nt, 2 = sc1 write-through, 3 = plain).  All variants
-                         * of one problem give bit-identical results.  Bit 17 forces the strip kernel (round 5; see mtp_gemm_nt_tile), bit 18
-                         * forbids it.  TN grouped: bit 19 = the plain phase instead of the read-ahead phase (round 5 A/B).  (Bits 7, 11-14
-                         * selected kernels that were removed in round 4 -- tools/ablation/ -- and are ignored.) */
+    int variant;        /* 0 = default kernels and heuristics; else an OR of mtp_gemm_variant flags (A/B choices, debug / tests) */
     float* colsum;      /* TN only, optional: colsum[m] += sum_k A[k][m]  (f32, M entries, ACCUMULATES) -- the bias
                          * gradient db = sum_rows dY comes out of the dW = dY^T X GEMM that streams dY anyway  */
     int defer_sum;      /* TN with a split-K workspace: 1 = leave the partial tiles in `aux`; the caller reduces them
@@ -89,11 +113,27 @@ typedef struct {
 /* y = x W^T (+epilogue): nn.Linear fwd/dgrad (VIT:50,52,78,87,256,262), patch-embed conv as GEMM (VIT:529),
  * ConvTranspose2d(2,2) as GEMM (VIT:642-649).  C[m][n] = sum_k A[m][k] * B[n][k]. */
 int mtp_gemm_nt(const mtp_gemm_args* args, mtp_stream_t stream);
-/* Query: the kernel family mtp_gemm_nt runs these arguments on, named by its tile -- 256 = the 8-wave pipelined
- * 256 x 256 x 64 kernel (bf16, K % 128 == 0, M % 8 == 0, N % 8 == 0), 64 = the strip kernel (round 5: 128 x 256 strips of
- * 64 x 64 wave blocks with two accumulator sets, the epilogue of a strip computed under the next strip's K loop; bf16,
- * K % 64 == 0, K >= 704), 128 = the 128-wide kernels (every other case, and f32).
+/* Query, no launch: the plan mtp_gemm_nt follows for these arguments on a stream of `cus` compute units (cus <= 0: the device's; 256 when there
+ * is none).  mtp_gemm_nt dispatches on the same plan.  Checks what the plan depends on (pointers, sizes, leading dimensions), not the epilogue's side inputs.
  * All families accumulate in the same k order: results are bit-identical. */
+typedef enum {
+    MTP_GEMM_NT_FAMILY_SB = 0,     /* 128 x 128 tiles, 4 waves, one LDS stage (both precisions, K in whole K-tiles) */
+    MTP_GEMM_NT_FAMILY_SB8 = 1,    /* 256 x 128 tiles, 8 waves, one LDS stage */
+    MTP_GEMM_NT_FAMILY_REG = 2,    /* 128 x 128 tiles staged through registers (ragged K, or MTP_GEMM_NT_REG_STAGED) */
+    MTP_GEMM_NT_FAMILY_P8 = 3,     /* 8-wave 8-phase pipelined kernel, 224 / 256 x 256 x 64 tiles (bf16, K % 128 == 0, M % 8 == 0, N % 8 == 0) */
+    MTP_GEMM_NT_FAMILY_STRIP = 4   /* strip kernel: 128 x 256 strips of 64 x 64 wave blocks with two accumulator sets, the epilogue of a strip computed under
+                                    * the next strip's K loop (bf16, K % 64 == 0, K >= 704) */
+} mtp_gemm_nt_family;
+struct mtp_gemm_nt_plan {
+    int family;       /* mtp_gemm_nt_family */
+    int tile_m;       /* rows per tile: 128, 224 or 256 */
+    int order;        /* tile order as the family's kernel reads it.  SB / SB8: 0 row-major with XCD remap, 1 blockIdx order, 2 panels of 8 tile rows;
+                       * REG: the raw order field;  P8 / STRIP: 1 = blockIdx order, 0 = XCD remap */
+    int persistent;   /* 1 = one workgroup per CU walks several tiles (P8: the persistent form; STRIP: always) */
+    int store_policy; /* stores of the epilogue: 1 nt, 2 sc1, 3 plain (the numbering of the MTP_GEMM_STORE_* field) */
+};
+int mtp_gemm_nt_plan(const mtp_gemm_args* args, int cus, struct mtp_gemm_nt_plan* out);
+/* The plan's family named by its tile, on the device's CUs: 256 = P8, 64 = STRIP, 128 = the 128-wide families SB, SB8 and REG (and f32). */
 int mtp_gemm_nt_tile(const mtp_gemm_args* args);
 /* bytes of `workspace` mtp_gemm_nt wants: 0 since round 4 (kept in the ABI for callers compiled against 0.3) */
 int64_t mtp_gemm_nt_workspace_bytes(void);
@@ -101,10 +141,11 @@ int64_t mtp_gemm_nt_workspace_bytes(void);
 int mtp_gemm_tn(const mtp_gemm_args* args, mtp_stream_t stream);
 /* Grouped weight gradients: `count` (<= MTP_MAX_GROUPED_GEMMS) independent problems C_i (M_i, N_i) f32 = A_i (K_i, M_i)^T B_i (K_i, N_i)
  * (+ colsum_i += column sums of A_i) in ONE launch of 256 x 256 output tiles, each workgroup running the whole contraction of
- * its tile through the 8-phase pipeline (no split-K, no partial tiles).  Meant for the weight gradients of several transformer
+ * its tile through the 8-phase pipeline (by default no split-K, no partial tiles).  Meant for the weight gradients of several transformer
  * blocks at once (4 ViT-L blocks = 768 tiles = three full rounds of the 256 CUs); results overwrite C_i.  Every problem must be
- * bf16 in / f32 out with M_i % 256 == 0, N_i % 256 == 0, K_i % 128 == 0; otherwise MTP_ERR_UNSUPPORTED and nothing is launched
- * (use mtp_gemm_tn per problem).  Fields epilogue / bias / res / aux / split_k / defer_sum of the entries are ignored. */
+ * bf16 in / f32 out with M_i % 8 == 0, N_i % 8 == 0 (edge tiles of the 256 x 256 grid are clamped / masked), K_i % 128 == 0 and lda, ldb multiples of 8;
+ * otherwise MTP_ERR_UNSUPPORTED and nothing is launched (use mtp_gemm_tn per problem).  split_k > 1 needs `aux` (f32, split_k * M * ldc): the pieces are summed into
+ * C unless defer_sum.  Of `variant`, the MTP_GEMM_TNG_* flags of args[0] hold for the whole launch.  Fields epilogue / bias / res of the entries are ignored. */
 #define MTP_MAX_GROUPED_GEMMS 32
 int mtp_gemm_tn_grouped(const mtp_gemm_args* args, int count, mtp_stream_t stream);
 /* out[i] = sum over `splits[i]` partial tiles of numel[i] f32 each, stored back to back at parts[i] -- the deferred split-K

@@ -12,6 +12,20 @@ LIB_PATH = os.environ.get("MTP_HIP_LIB") or os.path.join(_HERE, "libmtp_hip.so")
 MTP_F32, MTP_BF16, MTP_F64 = 0, 1, 2      # (MTP_F64: the DCNv3 entry points only)
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RES, EPI_DGELU, EPI_BIAS_GELU_DG, EPI_MUL = 0, 1, 2, 3, 4, 5
 
+# enum mtp_gemm_variant (GemmArgs.variant), same names without the MTP_ prefix; tests/test_abi.py checks them against the header
+GEMM_NT_REG_STAGED = 1
+GEMM_ORDER_SHIFT, GEMM_ORDER_PLAIN, GEMM_ORDER_GROUPED, GEMM_ORDER_ROW_MAJOR, GEMM_ORDER_MASK = 1, 1 << 1, 2 << 1, 3 << 1, 3 << 1
+GEMM_TNG_PLAIN_ORDER = 1 << 1
+GEMM_TN_REG_TRANSPOSE = 1 << 4
+GEMM_NT_SB8, GEMM_NT_NO_SB8 = 1 << 5, 1 << 6
+GEMM_NT_P8, GEMM_NT_P8_224, GEMM_NT_P8_256, GEMM_NT_P8_MASK, GEMM_NT_NO_P8 = 1 << 8, 2 << 8, 3 << 8, 3 << 8, 1 << 10
+GEMM_NT_PERSIST, GEMM_TN_TR_FULL_ONLY, GEMM_NT_NO_PERSIST = 1 << 15, 1 << 15, 1 << 16
+GEMM_NT_STRIP, GEMM_NT_NO_STRIP = 1 << 17, 1 << 18
+GEMM_TNG_PLAIN_PHASES = 1 << 19
+GEMM_STORE_SHIFT, GEMM_STORE_NT, GEMM_STORE_SC1, GEMM_STORE_PLAIN, GEMM_STORE_MASK = 20, 1 << 20, 2 << 20, 3 << 20, 3 << 20
+# enum mtp_gemm_nt_family (GemmNtPlan.family)
+GEMM_NT_FAMILY_SB, GEMM_NT_FAMILY_SB8, GEMM_NT_FAMILY_REG, GEMM_NT_FAMILY_P8, GEMM_NT_FAMILY_STRIP = 0, 1, 2, 3, 4
+
 p, i64, i32, f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
 
 
@@ -23,6 +37,11 @@ class GemmArgs(C.Structure):
                 ("rowscale", p), ("rows_per_sample", i64), ("aux", p), ("aux_ld", i64),
                 ("split_k", i32), ("variant", i32), ("colsum", p), ("defer_sum", i32), ("pad_", i32),
                 ("workspace", p), ("workspace_bytes", i64)]
+
+
+class GemmNtPlan(C.Structure):
+    """struct mtp_gemm_nt_plan"""
+    _fields_ = [("family", i32), ("tile_m", i32), ("order", i32), ("persistent", i32), ("store_policy", i32)]
 
 
 class WimgDesc(C.Structure):
@@ -50,6 +69,7 @@ SIGNATURES = {
     "mtp_dcnv3_bwd": (i32, [p, p, p, p, i32, p, p, p, C.POINTER(Dcnv3Geom), p]),
     "mtp_dcnv3_bwd_act": (i32, [p, p, p, p, i32, p, p, p, p, i64, C.POINTER(Dcnv3Geom), p]),
     "mtp_gemm_nt": (i32, [C.POINTER(GemmArgs), p]),
+    "mtp_gemm_nt_plan": (i32, [C.POINTER(GemmArgs), i32, C.POINTER(GemmNtPlan)]),
     "mtp_gemm_nt_tile": (i32, [C.POINTER(GemmArgs)]),
     "mtp_gemm_nt_workspace_bytes": (i64, []),
     "mtp_gemm_tn": (i32, [C.POINTER(GemmArgs), p]),

@@ -1505,6 +1505,8 @@ extern "C" int mtp_scale_rows_cast(const float* src, void* dst, int dst_dtype, c
 // 0.6: round 6 -- mtp_wimg_desc.pad_ became `float wd` (same size; read only by mtp_adamw_weight_images); new entry points mtp_adamw_weight_images, mtp_stream_create_cu_mask,
 // mtp_probe_placement, mtp_comm_info.  Later additions, no struct changed: mtp_adamw_flat_lr / mtp_adamw_weight_images_lr (layer-wise lr decay: a per-segment /
 // per-descriptor lr scale in a device table of its own).
+// mtp_gemm_nt_plan (the dispatch of mtp_gemm_nt as a query; mtp_gemm_nt_tile wraps it) and the enum mtp_gemm_variant naming the bits of mtp_gemm_args.variant at their
+// old values: no struct changed.
 extern "C" const char* mtp_version(void) { return "mtp_hip 0.6 (gfx950)"; }
 
 // A stream of the LOWEST priority the device offers (non-blocking), for work that is off the critical path and should only take the CUs

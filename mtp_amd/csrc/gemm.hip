@@ -85,7 +85,7 @@ __device__ __forceinline__ void stage_nt_glds(const KArgs& p, char* sA, char* sB
     }
 }
 
-// ---- NT staging through registers (variant 1; also handles ragged K) --------------------------------------------------
+// ---- NT staging through registers (MTP_GEMM_NT_REG_STAGED; also handles ragged K) --------------------------------------------------
 template <typename T>
 struct NtRegs {
     uint4 a[4], b[4];
@@ -123,7 +123,7 @@ __device__ __forceinline__ void store_nt_regs(const NtRegs<T>& r, char* sA, char
     }
 }
 
-template <typename T, typename Tout, int EPI, bool GLDS>
+template <typename T, typename Tout, int EPI>
 __global__ __launch_bounds__(NT_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_nt_kernel(KArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -139,30 +139,18 @@ __global__ __launch_bounds__(NT_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     const int nk = p.k_tiles;
-    if (GLDS) {
-        stage_nt_glds<T>(p, smem, smem + OPER_BYTES, m0, n0, 0, wave, lane);
-        for (int kt = 0; kt < nk; ++kt) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            char* cur = smem + (kt & 1) * STAGE_BYTES;
-            char* nxt = smem + ((kt + 1) & 1) * STAGE_BYTES;
-            if (kt + 1 < nk) stage_nt_glds<T>(p, nxt, nxt + OPER_BYTES, m0, n0, kt + 1, wave, lane);
-            compute_stage<T>(cur, cur + OPER_BYTES, acc, wm, wn, lane);
-        }
-    } else {
-        NtRegs<T> r;
-        load_nt_regs<T>(p, r, m0, n0, 0, tid);
-        store_nt_regs<T>(r, smem, smem + OPER_BYTES, tid);
-        for (int kt = 0; kt < nk; ++kt) {
-            __syncthreads();
-            char* cur = smem + (kt & 1) * STAGE_BYTES;
-            char* nxt = smem + ((kt + 1) & 1) * STAGE_BYTES;
-            load_nt_regs<T>(p, r, m0, n0, kt + 1 < nk ? kt + 1 : kt, tid);   // unconditional prefetch (see gemm_tn_kernel)
-            __builtin_amdgcn_sched_barrier(0);
-            compute_stage<T>(cur, cur + OPER_BYTES, acc, wm, wn, lane);
-            __builtin_amdgcn_sched_barrier(0);
-            store_nt_regs<T>(r, nxt, nxt + OPER_BYTES, tid);
-        }
+    NtRegs<T> r;
+    load_nt_regs<T>(p, r, m0, n0, 0, tid);
+    store_nt_regs<T>(r, smem, smem + OPER_BYTES, tid);
+    for (int kt = 0; kt < nk; ++kt) {
+        __syncthreads();
+        char* cur = smem + (kt & 1) * STAGE_BYTES;
+        char* nxt = smem + ((kt + 1) & 1) * STAGE_BYTES;
+        load_nt_regs<T>(p, r, m0, n0, kt + 1 < nk ? kt + 1 : kt, tid);   // unconditional prefetch (see gemm_tn_kernel)
+        __builtin_amdgcn_sched_barrier(0);
+        compute_stage<T>(cur, cur + OPER_BYTES, acc, wm, wn, lane);
+        __builtin_amdgcn_sched_barrier(0);
+        store_nt_regs<T>(r, nxt, nxt + OPER_BYTES, tid);
     }
     epilogue<Tout, EPI, 4>(p, acc, m0 + wm * 64, n0 + wn * 64, lane);
 }
@@ -405,41 +393,6 @@ __global__ __launch_bounds__(NT_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     epilogue<float, MTP_EPI_BIAS, 4>(p, acc, m0 + wm * 64, n0 + wn * 64, lane);
 }
 
-// Single-LDS-stage TN variant (32 KiB, 3 workgroups per CU): the prefetched tile waits in registers during the MFMAs and is
-// written to the one stage between two barriers; the other resident workgroups cover the bubbles.
-template <typename T, bool FULL>
-__global__ __launch_bounds__(NT_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3))) void gemm_tn_sb_kernel(KArgs p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int tile = (p.order & 1) ? (int)blockIdx.x : xcd_remap(blockIdx.x, gridDim.x);
-    const int m0 = (tile / p.tiles_n) * BM, n0 = (tile % p.tiles_n) * BN;
-    const int kt0 = blockIdx.y * p.k_tiles_per_split;
-    int kt1 = kt0 + p.k_tiles_per_split;
-    kt1 = kt1 < p.k_tiles ? kt1 : p.k_tiles;
-    if (kt0 >= kt1) return;
-    p.C += (int64_t)blockIdx.y * p.split_stride * (int64_t)sizeof(float);
-    f32x4_t acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    TnRegs<T> r;
-    load_tn_regs<T, FULL>(p, r, m0, n0, kt0, tid);
-    store_tn_regs<T>(r, smem, tid);
-    for (int kt = kt0; kt < kt1; ++kt) {
-        __syncthreads();
-        const int ktn = kt + 1 < kt1 ? kt + 1 : kt;
-        load_tn_regs<T, FULL>(p, r, m0, n0, ktn, tid);
-        __builtin_amdgcn_sched_barrier(0);
-        compute_stage<T>(smem, smem + OPER_BYTES, acc, wm, wn, lane);
-        __builtin_amdgcn_sched_barrier(0);
-        __syncthreads();
-        store_tn_regs<T>(r, smem, tid);
-    }
-    epilogue<float, MTP_EPI_BIAS, 4>(p, acc, m0 + wm * 64, n0 + wn * 64, lane);
-}
-
 // ---- TN, bf16, complete tiles: LDS-DMA staging of the UNtransposed tiles + hardware transpose reads ----------------------
 // The register-transposing kernels above spend more LDS-pipe cycles on their 8 ds_write_b128 per thread and k-tile (13 cycles
 // each) plus the fragment reads than the SIMDs spend on MFMAs.  Here both operand tiles go HBM -> LDS as they lie in memory
@@ -575,43 +528,83 @@ int fill_common(const mtp_gemm_args* a, KArgs& k) {
     k.k_tiles = (int)((a->K + 8 * E - 1) / (8 * E));
     k.k_tiles_per_split = k.k_tiles;
     k.atomic_out = 0;
-    k.order = (a->variant >> 1) & 3;
+    k.order = 0;            // the launchers set it
     k.split_stride = 0;
     k.colsum = nullptr;
     return 0;
 }
 
-// which NT kernel family runs a bf16 problem: 0 = the 128-wide kernels of this file, else gemm_p8.hip: 1 = tile height picked per
-// problem (256 or 224 rows), 2 = 224-row tiles, 3 = 256-row tiles.  variant bits 8-9 force 1 / 2 / 3 (when the problem fits), bit 10
-// forbids the kernel; bits 11-14 select an ablation build (tools/ab_gemm.py).
-int nt_p8_mode(const mtp_gemm_args* a, const KArgs& k, int cus) {
-    if (a->in_dtype != MTP_BF16 || (a->variant & 1024) || !mtp_nt_p8_fits(k, a->out_dtype, a->epilogue)) return 0;
-    const int forced = (a->variant >> 8) & 3;
-    if (forced) return forced;
-    // default: the pipelined kernel once its 256-wide tiles occupy a good part of the 256 CUs (one workgroup per CU); below that the
-    // 128-wide kernels with 4 workgroups per CU spread a small problem better.  Measured on the ViT-L shapes (tools/ab_gemm.py):
-    // +15 % (N = 3072 / 4096, K = 1024) ... +25 % (N = 1024, K = 3072 / 4096), +23 % on the FPN GEMM; on the mid-size shapes of
-    // InternImage-XL's 768- / 1536-channel levels and of ViT-B at batch 32 (tools/probes/ab_gemm_mid.py, round 3): 96 tiles +6 % (K = 768) /
-    // +17 % (K = 3072), 75 tiles +3 % / +16 %, 48 tiles +5 % (K = 1536) / +14 % (K = 6144), but 64 tiles of which half are mostly edge
-    // (N = 432, K = 768) -19 %: from 72 tiles on, or from 40 when the contraction is long.
-    // (cus: the CUs of the stream, 256 unless it is CU-masked -- the thresholds are fractions of a round)
-    const int64_t tiles = ((a->M + 255) / 256) * ((a->N + 255) / 256) * 256 / cus;
-    return (tiles >= 72 || (tiles >= 40 && a->K >= 1536)) ? 1 : 0;
-}
+// What mtp_gemm_nt runs a problem on, for a stream of `cus` CUs: the launch switches on it and mtp_gemm_nt_plan reports it.  All families are
+// bit-identical, so a wrong turn here is a silent slowdown: tests/test_gemm_plan_host.py pins the decisions.
+NtPlan nt_plan(const mtp_gemm_args* a, const KArgs& k, int cus) {
+    // the one place that reads the NT flags of args.variant (mtp_gemm_variant)
+    const int ord = (a->variant & MTP_GEMM_ORDER_MASK) >> MTP_GEMM_ORDER_SHIFT;           // 0 auto, 1 plain blockIdx, 2 grouped, 3 row-major with XCD remap
+    const int p8_forced = (a->variant & MTP_GEMM_NT_P8_MASK) / MTP_GEMM_NT_P8;            // 0 no, 1 = tile height picked per problem, 2 = 224 rows, 3 = 256 rows
+    const int sp_forced = (a->variant & MTP_GEMM_STORE_MASK) >> MTP_GEMM_STORE_SHIFT;     // 0 = by epilogue, 1 = nt, 2 = sc1 write-through, 3 = plain
+    const bool reg_staged = a->variant & MTP_GEMM_NT_REG_STAGED, sb8_force = a->variant & MTP_GEMM_NT_SB8, sb8_forbid = a->variant & MTP_GEMM_NT_NO_SB8;
+    const bool p8_forbid = a->variant & MTP_GEMM_NT_NO_P8, persist_force = a->variant & MTP_GEMM_NT_PERSIST, persist_forbid = a->variant & MTP_GEMM_NT_NO_PERSIST;
+    const bool s8_force = a->variant & MTP_GEMM_NT_STRIP, s8_forbid = a->variant & MTP_GEMM_NT_NO_STRIP;
 
-// the strip kernel of gemm_s8.hip (two accumulator sets, the epilogue of a strip under the next strip's K loop): variant bit 17 forces
-// it (when the problem fits), bit 18 forbids it.
-int nt_s8_mode(const mtp_gemm_args* a, const KArgs& k, int cus) {
-    if (a->in_dtype != MTP_BF16 || (a->variant & (1024 | (1 << 18))) || ((a->variant >> 8) & 3) || !mtp_nt_s8_fits(k, a->out_dtype, a->epilogue)) return 0;
-    if (a->variant & (1 << 17)) return 1;
+    const bool bf16 = a->in_dtype == MTP_BF16;
+    // 256 x 256 tiles of the problem, scaled to a round of 256 CUs (cus: the CUs of the stream, 256 unless it is CU-masked -- the thresholds are fractions of a round)
+    const int64_t tiles = ((a->M + 255) / 256) * ((a->N + 255) / 256) * 256 / cus;
+    NtPlan p = {MTP_GEMM_NT_FAMILY_SB, BM, 0, 0, MTP_GEMM_STORE_PLAIN >> MTP_GEMM_STORE_SHIFT};
+
+    // the strip kernel of gemm_s8.hip (two accumulator sets, the epilogue of a strip under the next strip's K loop), forced when the problem fits, or by
     // default: problems of less than half a round of 256 x 256 tiles on the 256 CUs -- the 768- / 1536-channel levels of InternImage-XL, ViT-B at
     // batch 32 with N = C.  Measured (tools/ab_gemm.py, MTP_AB_SHAPES=mid; profiles/r05_ab_gemm_s8_strip_mid_shapes.txt): 6272 x 768 x 768
     // 17.1 -> 15.6 us, 6272 x 768 x 3072 45.4 -> 38.3, 8192 x 768 x 768 16.8 -> 15.4, 8192 x 768 x 3072 45.5 -> 38.8, 2048 x 1536 x 1536 26.0 -> 22.6,
     // 2048 x 1536 x 6144 83.3 -> 67.9 (twice as many work units, each half as long, the epilogue of all but the last hidden); from 225 tiles on the
     // 8-wave kernel wins (its loop moves 2/3 of the L2 -> LDS bytes per flop): 6272 x 2304 x 768 22.5 vs 29.0, every ViT-L shape 10-38 %.
     // Below 40 tiles (not measured with this kernel) the 128-wide kernels keep the problem: 4 x as many, smaller workgroups.
-    const int64_t tiles = ((a->M + 255) / 256) * ((a->N + 255) / 256) * 256 / cus;
-    return tiles >= 40 && tiles <= 128;
+    if (bf16 && !p8_forbid && !s8_forbid && !p8_forced && mtp_nt_s8_fits(k, a->out_dtype, a->epilogue) && (s8_force || (tiles >= 40 && tiles <= 128))) {
+        p.family = MTP_GEMM_NT_FAMILY_STRIP;
+        p.order = ord == 1;
+        p.persistent = 1;
+        p.store_policy = mtp_nt_s8_store_policy(a->out_dtype);
+        return p;
+    }
+    // the 8-wave pipelined kernel of gemm_p8.hip (whole K-tile pairs), forced when the problem fits, or by
+    // default: once its 256-wide tiles occupy a good part of the 256 CUs (one workgroup per CU); below that the
+    // 128-wide kernels with 4 workgroups per CU spread a small problem better.  Measured on the ViT-L shapes (tools/ab_gemm.py):
+    // +15 % (N = 3072 / 4096, K = 1024) ... +25 % (N = 1024, K = 3072 / 4096), +23 % on the FPN GEMM; on the mid-size shapes of
+    // InternImage-XL's 768- / 1536-channel levels and of ViT-B at batch 32 (tools/probes/ab_gemm_mid.py, round 3): 96 tiles +6 % (K = 768) /
+    // +17 % (K = 3072), 75 tiles +3 % / +16 %, 48 tiles +5 % (K = 1536) / +14 % (K = 6144), but 64 tiles of which half are mostly edge
+    // (N = 432, K = 768) -19 %: from 72 tiles on, or from 40 when the contraction is long.
+    if (bf16 && !p8_forbid && mtp_nt_p8_fits(k, a->out_dtype, a->epilogue) && (p8_forced || tiles >= 72 || (tiles >= 40 && a->K >= 1536))) {
+        p.family = MTP_GEMM_NT_FAMILY_P8;
+        p.tile_m = p8_forced == 2 ? 224 : p8_forced == 3 ? 256 : mtp_nt_p8_pick_tile_m(k.M, k.N, cus);
+        p.order = ord == 1;
+        // persistent tiles: default for problems of more than one round of 224-row tiles (measured, tools/ab_gemm.py: +3...4 % at N = 3072 /
+        // 4096, K = 1024 and on the FPN GEMM, nothing to gain on one-round problems; the 256-row instantiations spill 2-17 VGPRs with the
+        // second tile loop and stay opt-in)
+        p.persistent = persist_force || (!persist_forbid && p.tile_m == 224 && mtp_nt_p8_tiles(k.M, k.N, p.tile_m) > cus);
+        // store policy of the epilogue.  Measured with rotating output buffers (tools/ab_gemm.py, MTP_AB_ROTATE=8: in the training step every GEMM
+        // writes fresh memory) and in the step itself (profiles/r03_ab_store_policy.txt): nt wins for the bf16 outputs (+2...4 %), sc1 for the f32
+        // residual epilogue (+1...5 %: its 103 MB of output per launch do not evict the operand panels from the 4-MiB L2s); whole step +1.0 %.
+        // Only the 224-row instantiations have the nt / sc1 stores
+        const int sp = sp_forced ? sp_forced : (a->epilogue == MTP_EPI_BIAS_RES ? 2 : 1);
+        if (p.tile_m == 224) p.store_policy = sp;
+        return p;
+    }
+    // 128-wide kernels.  Single-stage / 4 workgroups per CU (round 1: +20 % over a double-buffered 2-per-CU LDS-DMA kernel on every ViT-L shape; that
+    // kernel is gone since round 4 -- the register-staged form stays for ragged K and as MTP_GEMM_NT_REG_STAGED; it keeps its own meaning of the order bits)
+    if (reg_staged || a->K % (8 * (bf16 ? 8 : 4))) {
+        p.family = MTP_GEMM_NT_FAMILY_REG;
+        p.order = ord;
+        return p;
+    }
+    // tile order of the single-stage kernels.  Grouped (panels of 8 tile rows) measured +2..7 % at N = 3072 and +8..11 % at N = 4096, -2..3 % at N = 1024.
+    p.order = ord == 0 ? (k.tiles_n > 8 ? 2 : 0) : ord == 1 ? 1 : ord == 2 ? 2 : 0;
+    // 256 x 128 tile / 8 waves when the whole problem is ONE round of such workgroups on the 256 CUs (2 per CU) and every CU
+    // gets at least one: measured on M = 12544, N = 1024 (392 workgroups): +7.5 % (K = 1024), +17..18 % (K = 3072, 4096; up to
+    // 1095 TF/s); with several rounds (N = 3072: equal, N = 4096: -5 %) the coarser tiles lose to the tail.
+    const int tiles8 = ((k.M + NT8_BM - 1) / NT8_BM) * k.tiles_n;
+    if (sb8_force || (tiles8 >= 256 && tiles8 <= 512 && !sb8_forbid)) {
+        p.family = MTP_GEMM_NT_FAMILY_SB8;
+        p.tile_m = NT8_BM;
+    }
+    return p;
 }
 
 template <typename T, typename Tout, int EPI>
@@ -624,40 +617,16 @@ int launch_nt(const mtp_gemm_args* a, hipStream_t stream) {
     if (EPI == MTP_EPI_BIAS_RES && (!a->res || (a->res_ld % 4))) return MTP_ERR_ARG;
     if ((EPI == MTP_EPI_BIAS_GELU || EPI == MTP_EPI_DGELU || EPI == MTP_EPI_BIAS_GELU_DG || EPI == MTP_EPI_MUL) && (!a->aux || (a->aux_ld % 4))) return MTP_ERR_ARG;
     if (a->bias && a->bias_mod > 0 && (a->bias_mod % 4)) return MTP_ERR_ARG;
-    // 8-wave pipelined kernel (gemm_p8.hip; bf16, whole K-tile pairs): variant bits 8-9 pick the tile height (1 auto, 2 = 224 rows,
-    // 3 = 256 rows), bits 11-14 an ablation build, bits 15 / 16 force / forbid persistent tiles; falls through to the 128-wide kernels
-    // when the problem does not fit it
-    if constexpr (sizeof(T) == 2) {
-        const int cus = mtp_stream_cus(stream);
-        if (nt_s8_mode(a, k, cus)) return mtp_nt_s8_launch(k, a->out_dtype, EPI, ((((a->variant >> 1) & 3) == 1) ? 2 : 0), stream);
-        const int p8 = nt_p8_mode(a, k, cus);
-        if (p8) return mtp_nt_p8_launch(k, a->out_dtype, EPI, (p8 == 2 ? 1 : p8 == 3 ? 4 : 0) | ((((a->variant >> 1) & 3) == 1) ? 2 : 0) | (((a->variant >> 15) & 3) << 8) | (((a->variant >> 20) & 3) << 13), stream);
+    const NtPlan plan = nt_plan(a, k, mtp_stream_cus(stream));
+    k.order = plan.order;
+    const int tiles = (k.M + plan.tile_m - 1) / plan.tile_m * k.tiles_n;   // (the 128-wide families)
+    switch (plan.family) {
+        case MTP_GEMM_NT_FAMILY_STRIP: return mtp_nt_s8_launch(k, a->out_dtype, EPI, plan.order, stream);
+        case MTP_GEMM_NT_FAMILY_P8: return mtp_nt_p8_launch(k, a->out_dtype, EPI, plan, stream);
+        case MTP_GEMM_NT_FAMILY_SB8: hipLaunchKernelGGL((gemm_nt_sb8_kernel<T, Tout, EPI>), dim3(tiles), dim3(NT8_THREADS), NT8_STAGE_BYTES, stream, k); break;
+        case MTP_GEMM_NT_FAMILY_REG: hipLaunchKernelGGL((gemm_nt_kernel<T, Tout, EPI>), dim3(tiles), dim3(NT_THREADS), LDS_BYTES, stream, k); break;
+        default: hipLaunchKernelGGL((gemm_nt_sb_kernel<T, Tout, EPI>), dim3(tiles), dim3(NT_THREADS), STAGE_BYTES, stream, k);
     }
-    const int tiles_m = (k.M + BM - 1) / BM;
-    dim3 grid(tiles_m * k.tiles_n), block(NT_THREADS);
-    const bool glds = ((a->variant & 1) == 0) && (a->K % (8 * E) == 0);
-    // single-stage / 4 workgroups per CU (round 1: +20 % over a double-buffered 2-per-CU LDS-DMA kernel on every ViT-L shape; that kernel
-    // is gone since round 4 -- the register-staged form below stays for ragged K and as variant bit 0)
-    // tile order of the single-stage kernel: variant bits 1-2 = 0 auto, 1 plain blockIdx, 2 grouped, 3 row-major with XCD remap.
-    // Grouped (panels of 8 tile rows) measured +2..7 % at N = 3072 and +8..11 % at N = 4096, -2..3 % at N = 1024.
-    const int ord = (a->variant >> 1) & 3;
-    k.order = ord == 0 ? (k.tiles_n > 8 ? 2 : 0) : ord == 1 ? 1 : ord == 2 ? 2 : 0;
-    if (!glds) k.order = ord;   // the register-staged kernel keeps its own meaning of the bits
-    // 256 x 128 tile / 8 waves when the whole problem is ONE round of such workgroups on the 256 CUs (2 per CU) and every CU
-    // gets at least one: measured on M = 12544, N = 1024 (392 workgroups): +7.5 % (K = 1024), +17..18 % (K = 3072, 4096; up to
-    // 1095 TF/s); with several rounds (N = 3072: equal, N = 4096: -5 %) the coarser tiles lose to the tail.  Variant bit 5
-    // forces it, bit 6 forbids it.
-    const int tiles_m8 = (k.M + NT8_BM - 1) / NT8_BM;
-    const bool one_round = tiles_m8 * k.tiles_n >= 256 && tiles_m8 * k.tiles_n <= 512;
-    if (glds && ((a->variant & 32) || (one_round && !(a->variant & 64)))) {
-        if (ord == 0) k.order = k.tiles_n > 8 ? 2 : 0;
-        hipLaunchKernelGGL((gemm_nt_sb8_kernel<T, Tout, EPI>), dim3(tiles_m8 * k.tiles_n), dim3(NT8_THREADS), NT8_STAGE_BYTES, stream, k);
-        return mtp_launch_status();
-    }
-    if (glds)
-        hipLaunchKernelGGL((gemm_nt_sb_kernel<T, Tout, EPI>), grid, block, STAGE_BYTES, stream, k);
-    else
-        hipLaunchKernelGGL((gemm_nt_kernel<T, Tout, EPI, false>), grid, block, LDS_BYTES, stream, k);
     return mtp_launch_status();
 }
 
@@ -668,6 +637,9 @@ int launch_tn(const mtp_gemm_args* a, hipStream_t stream) {
     int rc = fill_common<T>(a, k);
     if (rc) return rc;
     if (a->out_dtype != MTP_F32 || (a->M % E) || (a->N % E)) return MTP_ERR_ARG;
+    // the one place that reads the TN flags of args.variant (mtp_gemm_variant)
+    const int ord = (a->variant & MTP_GEMM_ORDER_MASK) >> MTP_GEMM_ORDER_SHIFT;   // 0 auto, 1 plain blockIdx, 2 M-fastest, 3 N-fastest
+    const bool reg_transpose = a->variant & MTP_GEMM_TN_REG_TRANSPOSE, tr_full_only = a->variant & MTP_GEMM_TN_TR_FULL_ONLY;
     k.bias = nullptr;
     int split = a->split_k > 1 ? a->split_k : 1;
     if (split > k.k_tiles) split = k.k_tiles;
@@ -693,21 +665,19 @@ int launch_tn(const mtp_gemm_args* a, hipStream_t stream) {
     const int tiles_m = (k.M + BM - 1) / BM;
     dim3 grid(tiles_m * k.tiles_n, split), block(NT_THREADS);
     const bool full = (a->K % (8 * E) == 0) && (a->M % BM == 0) && (a->N % BN == 0);
-    // bf16 complete tiles: LDS-DMA + transpose-read kernel; variant bit 4 falls back to the register-transposing kernels
+    // bf16 complete tiles: LDS-DMA + transpose-read kernel, unless the register-transposing kernels are asked for
     // (the transpose-read kernel also takes edge tiles as long as the rows split into whole 16-byte chunks and K into whole 64-row stages)
-    const bool tr = sizeof(T) == 2 && !(a->variant & 16) && (full || ((a->K % 64 == 0) && (a->M % 8 == 0) && (a->N % 8 == 0) && a->M >= 8 && a->N >= 8 && !(a->variant & 32768)));
+    const bool tr = sizeof(T) == 2 && !reg_transpose && (full || ((a->K % 64 == 0) && (a->M % 8 == 0) && (a->N % 8 == 0) && a->M >= 8 && a->N >= 8 && !tr_full_only));
+    k.order = ord;            // (the register-transposing kernels read the raw field)
     if (a->colsum && !tr) {   // the other kernels do not produce the column sums: separate streaming pass over A
         rc = mtp_colsum_acc(a->A, a->in_dtype, a->lda, a->colsum, a->K, a->M, stream);
         if (rc) return rc;
     }
     if (tr) {
         k.colsum = a->colsum;
-        const int ord = (a->variant >> 1) & 3;   // 0 auto, 1 plain blockIdx, 2 M-fastest, 3 N-fastest
         k.order = ord == 0 ? (a->N > a->M ? 2 : 0) : ord == 1 ? 1 : ord == 2 ? 2 : 0;
         hipLaunchKernelGGL(gemm_tn_tr_kernel, grid, block, STAGE_BYTES, stream, k);
-    } else if (full && (a->variant & 8))
-        hipLaunchKernelGGL((gemm_tn_sb_kernel<T, true>), grid, block, STAGE_BYTES, stream, k);
-    else if (full)
+    } else if (full)
         hipLaunchKernelGGL((gemm_tn_kernel<T, true>), grid, block, LDS_BYTES, stream, k);
     else
         hipLaunchKernelGGL((gemm_tn_kernel<T, false>), grid, block, LDS_BYTES, stream, k);
@@ -773,14 +743,18 @@ extern "C" int mtp_gemm_nt(const mtp_gemm_args* a, mtp_stream_t stream) {
 // (round 4: the stream-K form that used `workspace` was removed -- measured slower; the query stays in the ABI and answers 0)
 extern "C" int64_t mtp_gemm_nt_workspace_bytes(void) { return 0; }
 
-extern "C" int mtp_gemm_nt_tile(const mtp_gemm_args* a) {
-    if (!a || !a->A || !a->B || !a->C || a->M <= 0 || a->N <= 0 || a->K <= 0) return MTP_ERR_ARG;
-    if (a->in_dtype != MTP_BF16) return 128;
+extern "C" int mtp_gemm_nt_plan(const mtp_gemm_args* a, int cus, struct mtp_gemm_nt_plan* out) {
+    if (!a || !out) return MTP_ERR_ARG;
     KArgs k;
-    if (fill_common<bf16_t>(a, k)) return MTP_ERR_ARG;
-    const int cus = mtp_stream_cus(nullptr);
-    if (nt_s8_mode(a, k, cus)) return 64;
-    return nt_p8_mode(a, k, cus) ? 256 : 128;
+    if (a->in_dtype == MTP_BF16 ? fill_common<bf16_t>(a, k) : fill_common<float>(a, k)) return MTP_ERR_ARG;
+    *out = nt_plan(a, k, cus > 0 ? cus : mtp_stream_cus(nullptr));
+    return 0;
+}
+
+extern "C" int mtp_gemm_nt_tile(const mtp_gemm_args* a) {
+    NtPlan p;
+    if (const int rc = mtp_gemm_nt_plan(a, 0, &p)) return rc;
+    return p.family == MTP_GEMM_NT_FAMILY_P8 ? 256 : p.family == MTP_GEMM_NT_FAMILY_STRIP ? 64 : 128;
 }
 
 extern "C" int mtp_sum_partials_batch(const float* const* parts, float* const* outs, const int64_t* numel, const int* splits, int count, mtp_stream_t stream) {

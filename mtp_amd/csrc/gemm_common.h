@@ -22,20 +22,24 @@ struct KArgs {
     int k_tiles;          // total k tiles
     int k_tiles_per_split;
     int atomic_out;
-    int order;              // tile order experiment: bit0 = no XCD remap, bit1 = M-fastest instead of N-fastest
+    int order;              // tile order as the kernel reads it (mtp_gemm_nt_plan.order; TN: bit0 = no XCD remap, bit1 = M-fastest instead of N-fastest)
     int64_t split_stride;   // TN split-K with workspace: partial tile of split z lives at C + z*split_stride (f32 elements)
     float* colsum;          // TN (transpose-read kernel): colsum[m] += sum_k A[k][m], or nullptr
 };
 
-// gemm_p8.hip: 256 x 256 x 64 tile, 8 waves, 8-phase LDS-DMA pipeline (bf16 NT, complete K tiles).  flags: bit0 = 224-row tiles,
-// bit2 = 256-row tiles (neither: picked per problem), bit1 = plain tile order (no XCD remap / grouping), bits 8 / 9 = force / forbid persistent tiles, bits 13-14 = store policy of the epilogue.  Returns MTP_ERR_UNSUPPORTED when the
-// problem does not fit the kernel's preconditions (the caller then uses the 128-wide kernels of gemm.hip).
-int mtp_nt_p8_launch(const KArgs& k, int out_dtype, int epilogue, int flags, hipStream_t stream);
+typedef struct mtp_gemm_nt_plan NtPlan;   // what mtp_gemm_nt runs a problem on (include/mtp_hip.h); filled by nt_plan() in gemm.hip, the only reader of the NT flags of args.variant
+
+// gemm_p8.hip: 224 / 256 x 256 x 64 tile, 8 waves, 8-phase LDS-DMA pipeline (bf16 NT, complete K tiles).  Runs what the plan says: tile_m, order, persistent,
+// store_policy.  Returns MTP_ERR_UNSUPPORTED when the problem does not fit the kernel's preconditions (nt_plan asks mtp_nt_p8_fits first).
+int mtp_nt_p8_launch(const KArgs& k, int out_dtype, int epilogue, const NtPlan& plan, hipStream_t stream);
 int mtp_nt_p8_fits(const KArgs& k, int out_dtype, int epilogue);   // 1 when mtp_nt_p8_launch would run the problem
+int mtp_nt_p8_tiles(int64_t M, int64_t N, int tile_m);             // tiles of tile_m rows the kernel cuts an (M, N) output into
+int mtp_nt_p8_pick_tile_m(int64_t M, int64_t N, int64_t cus);      // the cheaper of 256- and 224-row tiles on `cus` CUs
 // gemm_s8.hip: 128 x 256 x 64 strips, 8 waves, two accumulator sets: the epilogue of a strip runs under the next strip's K loop
-// (bf16 NT, K >= 704 in whole K-tiles).  flags: bit1 = plain strip order.  MTP_ERR_UNSUPPORTED when the problem does not fit.
-int mtp_nt_s8_launch(const KArgs& k, int out_dtype, int epilogue, int flags, hipStream_t stream);
+// (bf16 NT, K >= 704 in whole K-tiles).  order: 1 = plain strip order.  MTP_ERR_UNSUPPORTED when the problem does not fit.
+int mtp_nt_s8_launch(const KArgs& k, int out_dtype, int epilogue, int order, hipStream_t stream);
 int mtp_nt_s8_fits(const KArgs& k, int out_dtype, int epilogue);
+int mtp_nt_s8_store_policy(int out_dtype);                         // store policy of its epilogue (1 nt, 2 sc1)
 
 namespace {
 

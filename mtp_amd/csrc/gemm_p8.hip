@@ -110,7 +110,7 @@ struct NtOps {
 
 // MI1 = 4: 256 x 256 tile; MI1 = 3: 224 x 256 tile (wave rows of 112 = 64 + 48 rows).  M = 12544 tokens = 49 x 256 = 56 x 224: with
 // 256-row tiles every ViT-L shape runs 0.766 of a whole number of rounds on the 256 CUs (196 / 588 / 784 tiles), with 224-row tiles
-// 0.875 (224 / 672 / 896) at 7/8 of the time per tile -- the host picks the cheaper one per problem (p8_pick_bm).
+// 0.875 (224 / 672 / 896) at 7/8 of the time per tile -- the host picks the cheaper one per problem (mtp_nt_p8_pick_tile_m).
 // DMA source rows of this wave for output tile (m0, n0).  Piece q = 2 * wave + i holds rows [8q, 8q + 8) of the half tile image.
 //   A-half 0 (64 rows per wave row): image row 64 wr' + x  <->  tile row WROWS wr' + x         (wr' = q >> 3)
 //   A-half 1 (16 MI1 rows per wave row): image row 16 MI1 wr' + x  <->  tile row WROWS wr' + 64 + x; at MI1 = 3 the last four
@@ -151,7 +151,7 @@ __device__ __forceinline__ void p8_issue_prologue(P8Ctx& c) {
 
 // MI1 = 4: 256 x 256 tile; MI1 = 3: 224 x 256 tile (wave rows of 112 = 64 + 48 rows).  M = 12544 tokens = 49 x 256 = 56 x 224: with
 // 256-row tiles every ViT-L shape runs 0.766 of a whole number of rounds on the 256 CUs (196 / 588 / 784 tiles), with 224-row tiles
-// 0.875 (224 / 672 / 896) at 7/8 of the time per tile -- the host picks the cheaper one per problem (p8_pick_bm).
+// 0.875 (224 / 672 / 896) at 7/8 of the time per tile -- the host picks the cheaper one per problem (mtp_nt_p8_pick_tile_m).
 // PS = 1: persistent -- gridDim.x workgroups (one per CU) walk the tiles t = blockIdx.x, + gridDim.x, ...; when a tile's main loop
 // ends, the NEXT tile's first two K-tiles are issued into the (now idle) ring before the epilogue runs, and the epilogue transposes
 // through 4 KiB per wave beyond the ring: the first-load latency of a tile and the workgroup hand-over are hidden behind the
@@ -262,34 +262,17 @@ int launch_p8_kernel(const KArgs& a, int ntiles, hipStream_t stream) {
     return mtp_launch_status();
 }
 
-// rows per tile: whole rounds of one workgroup per CU cost (rows per tile) each -- take the cheaper of 256 and 224
-int p8_pick_bm(int64_t M, int64_t N, int64_t cus) {
-    const int64_t tn = (N + P8_BN - 1) / P8_BN;
-    const int64_t t256 = ((M + 255) / 256) * tn, t224 = ((M + 223) / 224) * tn;
-    const int64_t c256 = ((t256 + cus - 1) / cus) * 256, c224 = ((t224 + cus - 1) / cus) * 224;
-    return c224 < c256 ? 224 : 256;
-}
-
+// runs the plan (nt_plan, gemm.hip): tile_m 224 or 256 rows, persistent or one tile per workgroup, store policy 1 nt / 2 sc1 (224-row tiles only) / 3 plain
 template <typename Tout, int EPI>
-int launch_p8(const KArgs& k, int flags, hipStream_t stream) {
-    const int bm = (flags & 1) ? 224 : (flags & 4) ? 256 : p8_pick_bm(k.M, k.N, mtp_stream_cus(stream));
-    const int tiles_m = (k.M + bm - 1) / bm, tiles_n = (k.N + P8_BN - 1) / P8_BN;
+int launch_p8(const KArgs& k, const NtPlan& plan, hipStream_t stream) {
+    const int bm = plan.tile_m, sp = plan.store_policy;
+    const bool persist = plan.persistent;
     KArgs a = k;
-    a.tiles_n = tiles_n;
+    a.tiles_n = (k.N + P8_BN - 1) / P8_BN;
     a.k_tiles = k.K / 64;
-    a.order = (flags >> 1) & 1;
+    a.order = plan.order;
     a.atomic_out = 0;
-    const int ntiles = tiles_m * tiles_n;
-    // persistent tiles: default for problems of more than one round of 224-row tiles (measured, tools/ab_gemm.py: +3...4 % at N = 3072 /
-    // 4096, K = 1024 and on the FPN GEMM, nothing to gain on one-round problems; the 256-row instantiations spill 2-17 VGPRs with the
-    // second tile loop and stay opt-in).  flags bit 8 forces it, bit 9 forbids it (A/B).
-    const bool persist = (flags & 256) || (!(flags & 512) && bm == 224 && ntiles > mtp_stream_cus(stream));
-    // store policy of the epilogue (224-row tiles; flags bits 13-14: 0 = by epilogue, 1 = nt, 2 = sc1 write-through, 3 = plain).  Measured with
-    // rotating output buffers (tools/ab_gemm.py, MTP_AB_ROTATE=8: in the training step every GEMM writes fresh memory) and in the step
-    // itself (profiles/r03_ab_store_policy.txt): nt wins for the bf16 outputs (+2...4 %), sc1 for the f32 residual epilogue (+1...5 %:
-    // its 103 MB of output per launch do not evict the operand panels from the 4-MiB L2s); whole step +1.0 %.
-    int sp = (flags >> 13) & 3;
-    if (sp == 0) sp = (EPI == MTP_EPI_BIAS_RES) ? 2 : 1;
+    const int ntiles = mtp_nt_p8_tiles(k.M, k.N, bm);
     if (bm == 224 && sp == 1) return persist ? launch_p8_kernel<Tout, EPI, 3, 0, 1, 1>(a, ntiles, stream) : launch_p8_kernel<Tout, EPI, 3, 0, 0, 1>(a, ntiles, stream);
     if (bm == 224 && sp == 2) return persist ? launch_p8_kernel<Tout, EPI, 3, 0, 1, 2>(a, ntiles, stream) : launch_p8_kernel<Tout, EPI, 3, 0, 0, 2>(a, ntiles, stream);
     if (persist) {
@@ -301,13 +284,13 @@ int launch_p8(const KArgs& k, int flags, hipStream_t stream) {
 }
 
 template <typename Tout>
-int dispatch_p8(const KArgs& k, int epi, int flags, hipStream_t s) {
+int dispatch_p8(const KArgs& k, int epi, const NtPlan& plan, hipStream_t s) {
     switch (epi) {
-        case MTP_EPI_BIAS: return launch_p8<Tout, MTP_EPI_BIAS>(k, flags, s);
-        case MTP_EPI_BIAS_GELU: return launch_p8<Tout, MTP_EPI_BIAS_GELU>(k, flags, s);
-        case MTP_EPI_DGELU: return launch_p8<Tout, MTP_EPI_DGELU>(k, flags, s);
-        case MTP_EPI_BIAS_GELU_DG: return launch_p8<Tout, MTP_EPI_BIAS_GELU_DG>(k, flags, s);
-        case MTP_EPI_MUL: return launch_p8<Tout, MTP_EPI_MUL>(k, flags, s);
+        case MTP_EPI_BIAS: return launch_p8<Tout, MTP_EPI_BIAS>(k, plan, s);
+        case MTP_EPI_BIAS_GELU: return launch_p8<Tout, MTP_EPI_BIAS_GELU>(k, plan, s);
+        case MTP_EPI_DGELU: return launch_p8<Tout, MTP_EPI_DGELU>(k, plan, s);
+        case MTP_EPI_BIAS_GELU_DG: return launch_p8<Tout, MTP_EPI_BIAS_GELU_DG>(k, plan, s);
+        case MTP_EPI_MUL: return launch_p8<Tout, MTP_EPI_MUL>(k, plan, s);
         default: return MTP_ERR_UNSUPPORTED;
     }
 }
@@ -323,9 +306,18 @@ int mtp_nt_p8_fits(const KArgs& k, int out_dtype, int epi) {
     return out_dtype == MTP_F32 && epi == MTP_EPI_BIAS;
 }
 
-int mtp_nt_p8_launch(const KArgs& k, int out_dtype, int epi, int flags, hipStream_t stream) {
+int mtp_nt_p8_tiles(int64_t M, int64_t N, int tile_m) { return (int)(((M + tile_m - 1) / tile_m) * ((N + P8_BN - 1) / P8_BN)); }
+
+// rows per tile: whole rounds of one workgroup per CU cost (rows per tile) each -- take the cheaper of 256 and 224
+int mtp_nt_p8_pick_tile_m(int64_t M, int64_t N, int64_t cus) {
+    const int64_t t256 = mtp_nt_p8_tiles(M, N, 256), t224 = mtp_nt_p8_tiles(M, N, 224);
+    const int64_t c256 = ((t256 + cus - 1) / cus) * 256, c224 = ((t224 + cus - 1) / cus) * 224;
+    return c224 < c256 ? 224 : 256;
+}
+
+int mtp_nt_p8_launch(const KArgs& k, int out_dtype, int epi, const NtPlan& plan, hipStream_t stream) {
     if (!mtp_nt_p8_fits(k, out_dtype, epi)) return MTP_ERR_UNSUPPORTED;
-    if (epi == MTP_EPI_BIAS_RES) return launch_p8<float, MTP_EPI_BIAS_RES>(k, flags, stream);
-    if (out_dtype == MTP_BF16) return dispatch_p8<bf16_t>(k, epi, flags, stream);
-    return launch_p8<float, MTP_EPI_BIAS>(k, flags, stream);
+    if (epi == MTP_EPI_BIAS_RES) return launch_p8<float, MTP_EPI_BIAS_RES>(k, plan, stream);
+    if (out_dtype == MTP_BF16) return dispatch_p8<bf16_t>(k, epi, plan, stream);
+    return launch_p8<float, MTP_EPI_BIAS>(k, plan, stream);
 }

@@ -19,7 +19,7 @@
 // three DMA pieces per wave (the 256-row tile: 8 / 4 and two), and the read part, not the matrix pipe, is what both kernels' phases wait
 // for (profiles/r05_ab_p8_loop_ablations.txt).  It WINS where the 256 x 256 tiles leave most CUs idle: problems of 40-128 tiles (ViT-B at
 // batch 32 with N = C, InternImage-XL's 768- / 1536-channel levels) run 8-19 % faster on twice as many, half as long work units, and
-// that is where mtp_gemm_nt dispatches it (gemm.hip: nt_s8_mode).
+// that is where mtp_gemm_nt dispatches it (gemm.hip: nt_plan).
 //
 // Pipeline (same two-wave-group stagger, barriers and counted waits as gemm_p8.h; re-derived for 3 half tiles per K-tile):
 //   LDS ring = 3 K-tile buffers x { A (128 rows), B0, B1 (128 columns each: the 32-column sub-tile h of every wave column) },
@@ -537,18 +537,22 @@ __global__ __launch_bounds__(S8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     e.template flush_from<0, POL>(p);
 }
 
-template <typename Tout, int EPI, bool HASB, int POL>
-int launch_s8_kernel(const KArgs& k, int flags, hipStream_t stream) {
+// store policy of the epilogue (gemm_p8.h): nt for the bf16 outputs, sc1 write-through for the f32 ones
+template <typename Tout>
+constexpr int kS8Pol = sizeof(Tout) == 2 ? 1 : 2;
+
+template <typename Tout, int EPI, bool HASB>
+int launch_s8_kernel(const KArgs& k, int order, hipStream_t stream) {
     static unsigned long long optin = 0;   // 144 KiB of dynamic LDS needs the opt-in once per kernel and device
-    if (const int e = mtp_optin_lds((const void*)gemm_nt_s8_kernel<Tout, EPI, HASB, POL>, S8_LDS, optin)) return e;
+    if (const int e = mtp_optin_lds((const void*)gemm_nt_s8_kernel<Tout, EPI, HASB, kS8Pol<Tout>>, S8_LDS, optin)) return e;
     KArgs a = k;
     a.tiles_n = (k.N + S8_BN - 1) / S8_BN;
     a.k_tiles = k.K / 64;
-    a.order = (flags >> 1) & 1;
+    a.order = order;
     const int nstrips = ((k.M + S8_BM - 1) / S8_BM) * a.tiles_n;
     const int cus = mtp_stream_cus(stream);
     const int grid = nstrips < cus ? nstrips : cus;
-    hipLaunchKernelGGL((gemm_nt_s8_kernel<Tout, EPI, HASB, POL>), dim3(grid), dim3(S8_THREADS), S8_LDS, stream, a);
+    hipLaunchKernelGGL((gemm_nt_s8_kernel<Tout, EPI, HASB, kS8Pol<Tout>>), dim3(grid), dim3(S8_THREADS), S8_LDS, stream, a);
     return mtp_launch_status();
 }
 
@@ -570,12 +574,14 @@ int mtp_nt_s8_fits(const KArgs& k, int out_dtype, int epi) {
     return 0;
 }
 
-int mtp_nt_s8_launch(const KArgs& k, int out_dtype, int epi, int flags, hipStream_t stream) {
+int mtp_nt_s8_store_policy(int out_dtype) { return out_dtype == MTP_BF16 ? kS8Pol<bf16_t> : kS8Pol<float>; }
+
+int mtp_nt_s8_launch(const KArgs& k, int out_dtype, int epi, int order, hipStream_t stream) {
     if (!mtp_nt_s8_fits(k, out_dtype, epi)) return MTP_ERR_UNSUPPORTED;
     const bool hasb = k.bias != nullptr;
-    if (epi == MTP_EPI_BIAS_RES) return hasb ? launch_s8_kernel<float, MTP_EPI_BIAS_RES, true, 2>(k, flags, stream) : launch_s8_kernel<float, MTP_EPI_BIAS_RES, false, 2>(k, flags, stream);
-    if (epi == MTP_EPI_BIAS_GELU_DG) return launch_s8_kernel<bf16_t, MTP_EPI_BIAS_GELU_DG, true, 1>(k, flags, stream);
-    if (epi == MTP_EPI_MUL) return launch_s8_kernel<bf16_t, MTP_EPI_MUL, false, 1>(k, flags, stream);
-    if (out_dtype == MTP_BF16) return hasb ? launch_s8_kernel<bf16_t, MTP_EPI_BIAS, true, 1>(k, flags, stream) : launch_s8_kernel<bf16_t, MTP_EPI_BIAS, false, 1>(k, flags, stream);
-    return hasb ? launch_s8_kernel<float, MTP_EPI_BIAS, true, 2>(k, flags, stream) : launch_s8_kernel<float, MTP_EPI_BIAS, false, 2>(k, flags, stream);
+    if (epi == MTP_EPI_BIAS_RES) return hasb ? launch_s8_kernel<float, MTP_EPI_BIAS_RES, true>(k, order, stream) : launch_s8_kernel<float, MTP_EPI_BIAS_RES, false>(k, order, stream);
+    if (epi == MTP_EPI_BIAS_GELU_DG) return launch_s8_kernel<bf16_t, MTP_EPI_BIAS_GELU_DG, true>(k, order, stream);
+    if (epi == MTP_EPI_MUL) return launch_s8_kernel<bf16_t, MTP_EPI_MUL, false>(k, order, stream);
+    if (out_dtype == MTP_BF16) return hasb ? launch_s8_kernel<bf16_t, MTP_EPI_BIAS, true>(k, order, stream) : launch_s8_kernel<bf16_t, MTP_EPI_BIAS, false>(k, order, stream);
+    return hasb ? launch_s8_kernel<float, MTP_EPI_BIAS, true>(k, order, stream) : launch_s8_kernel<float, MTP_EPI_BIAS, false>(k, order, stream);
 }

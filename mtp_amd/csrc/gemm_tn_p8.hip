@@ -291,6 +291,9 @@ __global__ __launch_bounds__(P8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 extern "C" int mtp_gemm_tn_grouped(const mtp_gemm_args* args, int count, mtp_stream_t stream) {
     if (!args || count <= 0) return MTP_ERR_ARG;
     if (count > TN_MAX_PROBLEMS) return MTP_ERR_UNSUPPORTED;
+    // the one place that reads the grouped-TN flags of args.variant (mtp_gemm_variant); those of args[0] hold for the launch.  Read-ahead phases (gemm_p8.h: the
+    // next phase's transpose reads issued under the current phase's MFMAs; round 5: +5-11 %) unless the plain phases of rounds 2-4 are asked for (A/B, bit-identical)
+    const bool plain_order = args[0].variant & MTP_GEMM_TNG_PLAIN_ORDER, plain_phase = args[0].variant & MTP_GEMM_TNG_PLAIN_PHASES;
     TnGroup g = {};
     int64_t tiles = 0;
     for (int i = 0; i < count; ++i) {
@@ -324,10 +327,7 @@ extern "C" int mtp_gemm_tn_grouped(const mtp_gemm_args* args, int count, mtp_str
     }
     g.nprob = count;
     g.ntiles = (int)tiles;
-    g.plain = (args[0].variant >> 1) & 1;
-    // read-ahead phases (gemm_p8.h: the next phase's transpose reads issued under the current phase's MFMAs; round 5: +5-11 %); variant bit 19 = the
-    // plain phases of rounds 2-4 (A/B, bit-identical)
-    const int plain_phase = (args[0].variant >> 19) & 1;
+    g.plain = plain_order;
     void (*kern)(TnGroup) = plain_phase ? gemm_tn_p8_kernel<0, 0> : gemm_tn_p8_kernel<0, 1>;
     static unsigned long long optin[2] = {0, 0};     // 128 KiB of dynamic LDS: opt-in once per kernel INSTANTIATION and device
     if (const int e = mtp_optin_lds((const void*)kern, P8_LDS, optin[plain_phase])) return e;

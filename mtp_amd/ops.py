@@ -9,6 +9,10 @@ import torch
 from . import _lib
 from ._lib import (EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GELU_DG, EPI_BIAS_RES, EPI_DGELU, EPI_MUL, MTP_BF16, MTP_F32, GemmArgs,  # noqa: F401
                    check)
+from ._lib import (GEMM_NT_FAMILY_P8, GEMM_NT_FAMILY_REG, GEMM_NT_FAMILY_SB, GEMM_NT_FAMILY_SB8, GEMM_NT_FAMILY_STRIP, GEMM_NT_NO_P8,  # noqa: F401
+                   GEMM_NT_NO_PERSIST, GEMM_NT_NO_SB8, GEMM_NT_NO_STRIP, GEMM_NT_P8, GEMM_NT_P8_224, GEMM_NT_P8_256, GEMM_NT_PERSIST,
+                   GEMM_NT_REG_STAGED, GEMM_NT_SB8, GEMM_NT_STRIP, GEMM_ORDER_GROUPED, GEMM_ORDER_PLAIN, GEMM_ORDER_ROW_MAJOR, GEMM_STORE_NT,
+                   GEMM_STORE_PLAIN, GEMM_STORE_SC1, GEMM_TN_REG_TRANSPOSE, GEMM_TN_TR_FULL_ONLY, GEMM_TNG_PLAIN_ORDER, GEMM_TNG_PLAIN_PHASES)
 
 _DT = {torch.float32: MTP_F32, torch.bfloat16: MTP_BF16}
 def lib():
@@ -91,6 +95,16 @@ def gemm_nt_tile(a, w, out, epi=EPI_BIAS, bias=None, bias_mod=0, res=None, res_m
     if rc < 0:
         check(rc, "mtp_gemm_nt_tile")
     return rc
+
+
+def gemm_nt_plan(a, w, out, epi=EPI_BIAS, bias=None, bias_mod=0, res=None, res_mod=0, rowscale=None, rows_per_sample=0,
+                 aux=None, variant=0, n=None, cus=0):
+    """the plan gemm_nt(...) follows for these arguments on a stream of `cus` CUs (0: the device's), no launch: a _lib.GemmNtPlan
+    (family = GEMM_NT_FAMILY_*, tile_m, order, persistent, store_policy)"""
+    g = _nt_args(a, w, out, epi, bias, bias_mod, res, res_mod, rowscale, rows_per_sample, aux, variant, n)
+    plan = _lib.GemmNtPlan()
+    check(lib().mtp_gemm_nt_plan(C.byref(g), cus, C.byref(plan)), "mtp_gemm_nt_plan")
+    return plan
 
 
 def pick_split_k(M, N, K):

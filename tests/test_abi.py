@@ -22,6 +22,27 @@ def test_header_symbols_are_bound_and_exported():
     assert b"gfx950" in lib.mtp_version()
 
 
+def test_gemm_variant_flags_mirror_the_header():
+    """enum mtp_gemm_variant / mtp_gemm_nt_family and struct mtp_gemm_nt_plan against their mirrors in _lib (and the re-exports of ops' namespace)"""
+    import ctypes as C
+    from mtp_amd import _lib
+    src = open(os.path.join(ROOT, "include", "mtp_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    for enum, floor in (("mtp_gemm_variant", 25), ("mtp_gemm_nt_family", 5)):
+        body = re.search(r"typedef enum \{([^}]*)\}\s*%s;" % enum, src).group(1)
+        items = re.findall(r"MTP_(GEMM_[A-Z0-9_]+)\s*=\s*(\d+)(?:\s*<<\s*(\d+))?\s*(?:,|$)", body)
+        assert len(items) >= floor and len(items) == body.count("="), enum
+        for name, v, sh in items:
+            assert getattr(_lib, name) == int(v) << int(sh or 0), name
+        mirrored = [n for n in dir(_lib) if n.startswith("GEMM_") and (n.startswith("GEMM_NT_FAMILY_") == (enum == "mtp_gemm_nt_family"))]
+        assert sorted(mirrored) == sorted(n for n, _, _ in items), enum
+    # today's numbers are ABI: A/B libraries and recorded profiles refer to them
+    assert (_lib.GEMM_NT_REG_STAGED, _lib.GEMM_NT_SB8 | _lib.GEMM_ORDER_GROUPED, _lib.GEMM_NT_P8_224 | _lib.GEMM_ORDER_PLAIN, _lib.GEMM_NT_NO_P8) == (1, 36, 514, 1024)
+    assert (_lib.GEMM_NT_PERSIST, _lib.GEMM_NT_STRIP, _lib.GEMM_TNG_PLAIN_PHASES, _lib.GEMM_STORE_PLAIN, _lib.GEMM_TN_REG_TRANSPOSE) == (32768, 1 << 17, 1 << 19, 3 << 20, 16)
+    fields = re.findall(r"int (\w+);", re.search(r"struct mtp_gemm_nt_plan \{([^}]*)\};", src).group(1))
+    assert fields == [f for f, _ in _lib.GemmNtPlan._fields_] and C.sizeof(_lib.GemmNtPlan) == 4 * len(fields)
+
+
 def test_gemm_args_struct_layout():
     import ctypes as C
     from mtp_amd._lib import GemmArgs

@@ -15,6 +15,7 @@ import torch.nn.functional as F
 
 import guard
 from conftest import rel_err
+from mtp_amd._lib import GEMM_NT_P8, GEMM_NT_P8_224, GEMM_NT_P8_256, GEMM_NT_REG_STAGED, GEMM_NT_SB8, GEMM_NT_STRIP
 from oracle import vit_rvsa_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -86,9 +87,8 @@ def gemm_bound(K, mag, ref, out_dtype):
 
 
 # ------------------------------------------------------------------------------------------------ gemm_nt
-S8 = 1 << 17
-FAMILIES = [0, 1, 32]                         # the 128-wide kernels: default (LDS-DMA on whole K tiles) / register-staged / 256 x 128 8-wave
-FALL_THROUGH = [256, 512, 768, S8]            # pipelined (auto, 224, 256 rows) / strip: take none of the ragged shapes below
+FAMILIES = [0, GEMM_NT_REG_STAGED, GEMM_NT_SB8]                         # the 128-wide kernels: default (LDS-DMA on whole K tiles) / register-staged / 256 x 128 8-wave
+FALL_THROUGH = [GEMM_NT_P8, GEMM_NT_P8_224, GEMM_NT_P8_256, GEMM_NT_STRIP]            # pipelined (auto, 224, 256 rows) / strip: take none of the ragged shapes below
 MS, NS = [1, 7, 127, 129, 255, 257], [4, 12, 132, 260]
 KS = {BF16: [8, 72, 200, 64], F32: [4, 36, 100, 32]}       # ragged K (register-staged loads) and one whole K tile (64 bf16 / 32 f32: the LDS-DMA kernels)
 EPIS = ["none", "bias", "res_rowscale", "res_mod", "bias_mod", "gelu_aux", "gelu_dg", "mul", "n_slice"]
@@ -184,7 +184,7 @@ def _run_nt(ops, dtype, variant, M, N, K, epi, want_tile):
 @pytest.mark.parametrize("mi,ni,ki,epi", _nt_cases())
 def test_gemm_nt_edge_shapes(ops, dtype, variant, mi, ni, ki, epi):
     """M down to 1, N down to 4, a partial tile in both directions, K below and off the K tile, on the 128-wide kernels (LDS-DMA form for K = 64 / 32,
-    register-staged otherwise; 256 x 128 tiles with variant 32)"""
+    register-staged otherwise; 256 x 128 tiles with GEMM_NT_SB8)"""
     _run_nt(ops, dtype, variant, MS[mi], NS[ni], KS[dtype][ki], epi, 128)
 
 
@@ -192,8 +192,8 @@ def test_gemm_nt_edge_shapes(ops, dtype, variant, mi, ni, ki, epi):
 @pytest.mark.parametrize("variant", FALL_THROUGH)
 @pytest.mark.parametrize("mi,ni,ki,epi", _nt_cases(9))
 def test_gemm_nt_edge_shapes_fall_through(ops, dtype, variant, mi, ni, ki, epi):
-    """with these contractions (K < 128, or off 64) and row / column counts off 8, neither the pipelined (variant 256 / 512 / 768) nor the strip kernel
-    (bit 17) takes the problem: gemm_nt_tile must say 128, i.e. the forced variant falls through to the default kernel, and the result holds all the same.
+    """with these contractions (K < 128, or off 64) and row / column counts off 8, neither the pipelined (GEMM_NT_P8 / _224 / _256) nor the strip kernel
+    (GEMM_NT_STRIP) takes the problem: gemm_nt_tile must say 128, i.e. the forced variant falls through to the default kernel, and the result holds all the same.
     Nine cases each: every M, N, K and epilogue once (the kernel that runs is the one the 18 cases of variant 0 above already sweep)"""
     _run_nt(ops, dtype, variant, MS[mi], NS[ni], KS[dtype][ki], epi, 128)
 
@@ -201,7 +201,7 @@ def test_gemm_nt_edge_shapes_fall_through(ops, dtype, variant, mi, ni, ki, epi):
 # the smallest / most ragged problems the pipelined and the strip kernel themselves accept: M, N multiples of 8 from 8 up; K = 128 (one K-tile pair) resp.
 # 704 (11 K tiles) -- here gemm_nt_tile must name those families.  All nine epilogues: the pipelined kernel has an instantiation for each; the strip
 # kernel has none for GELU + aux and takes no res_mod (mtp_nt_s8_fits) -- those two must fall through to the 128-wide kernels, which is asserted.
-P8S8 = [(256, 256, 128), (512, 256, 128), (768, 256, 256), (S8, 64, 704)]
+P8S8 = [(GEMM_NT_P8, 256, 128), (GEMM_NT_P8_224, 256, 128), (GEMM_NT_P8_256, 256, 256), (GEMM_NT_STRIP, 64, 704)]
 P8S8_SHAPES = [(8, 8), (8, 264), (264, 8), (136, 136), (520, 24)]
 
 
@@ -211,7 +211,7 @@ def _p8s8_cases():
     for variant, tile, K in P8S8:
         for j in range(27):
             epi = EPIS[j % 9]
-            out.append((variant, 128 if variant == S8 and epi in ("res_mod", "gelu_aux") else tile, K) + P8S8_SHAPES[j % 5] + (epi,))
+            out.append((variant, 128 if variant == GEMM_NT_STRIP and epi in ("res_mod", "gelu_aux") else tile, K) + P8S8_SHAPES[j % 5] + (epi,))
     return out
 
 

@@ -7,6 +7,8 @@ import torch
 
 import guard
 from conftest import ROOT, rel_err
+from mtp_amd._lib import (GEMM_NT_NO_P8, GEMM_NT_NO_SB8, GEMM_NT_P8, GEMM_NT_P8_224, GEMM_NT_P8_256, GEMM_NT_PERSIST, GEMM_NT_REG_STAGED, GEMM_NT_SB8,
+                          GEMM_NT_STRIP, GEMM_ORDER_GROUPED, GEMM_ORDER_PLAIN, GEMM_STORE_NT, GEMM_STORE_PLAIN, GEMM_STORE_SC1, GEMM_TNG_PLAIN_PHASES)
 from oracle import vit_rvsa_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -65,7 +67,7 @@ def e(*shape, dtype=torch.float32):
 
 # ------------------------------------------------------------------------------------------------ GEMM
 @pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("variant", [0, 1, 32, 36])   # default / register-staged / 256x128 8-wave tile (+ grouped order)
+@pytest.mark.parametrize("variant", [0, GEMM_NT_REG_STAGED, GEMM_NT_SB8, GEMM_NT_SB8 | GEMM_ORDER_GROUPED])   # default / register-staged / 256x128 8-wave tile (+ grouped order)
 @pytest.mark.parametrize("M,N,K", [(392, 384, 128), (300, 256, 192), (1024, 768, 768), (128, 128, 64)])
 def test_gemm_nt_bias(ops, dtype, variant, M, N, K):
     a, w, b = rnd(M, K, dtype=dtype), rnd(N, K, dtype=dtype, seed=1), rnd(N, seed=2)
@@ -120,24 +122,24 @@ def test_gemm_nt_epilogues(ops, dtype):
 
 @pytest.mark.parametrize("dtype", DT)
 def test_gemm_nt_tile_variants_bit_identical(ops, dtype):
-    """the 256x128 / 8-wave kernel (variant 32; picked automatically for one-round problems such as M = 12544, N = 1024) and the
+    """the 256x128 / 8-wave kernel (GEMM_NT_SB8; picked automatically for one-round problems such as M = 12544, N = 1024) and the
     tile orders accumulate in the same k order as the default kernel: every epilogue must come out bit-identical"""
     M, N, K, rps = 1024, 384, 256, 256   # complete 128-row tiles
     a, w, b = dev(rnd(M, K, dtype=dtype), dtype), dev(rnd(N, K, dtype=dtype, seed=1, scale=0.2), dtype), dev(rnd(N, seed=2))
     res, rs, uu = dev(rnd(M, N, seed=3)), dev(torch.tensor([0.0, 1.1, 0.9, 1.0])), dev(rnd(M, N, dtype=dtype, seed=5), dtype)
     outs = {}
-    for v in (0, 32, 36, 4, 64):
+    for v in (0, GEMM_NT_SB8, GEMM_NT_SB8 | GEMM_ORDER_GROUPED, GEMM_ORDER_GROUPED, GEMM_NT_NO_SB8):
         u = e(M, N, dtype=dtype)
         h = ops.gemm_nt(a, w, e(M, N, dtype=dtype), epi=ops.EPI_BIAS_GELU, bias=b, aux=u, variant=v)
         r = ops.gemm_nt(a, w, e(M, N), epi=ops.EPI_BIAS_RES, bias=b, res=res, rowscale=rs, rows_per_sample=rps, variant=v)
         d = ops.gemm_nt(a, w, e(M, N, dtype=dtype), epi=ops.EPI_DGELU, aux=uu, variant=v)
         outs[v] = (u, h, r, d)
-    for v in (32, 36, 4, 64):
+    for v in (GEMM_NT_SB8, GEMM_NT_SB8 | GEMM_ORDER_GROUPED, GEMM_ORDER_GROUPED, GEMM_NT_NO_SB8):
         for x, y in zip(outs[0], outs[v]):
             assert torch.equal(x, y), v
 
 
-# ---- the 8-wave pipelined kernel (gemm_p8.hip): variant 256 = tile height picked per problem, 512 = 224 x 256 tiles, 768 = 256 x 256 tiles
+# ---- the 8-wave pipelined kernel (gemm_p8.hip): GEMM_NT_P8 = tile height picked per problem, GEMM_NT_P8_224 = 224 x 256 tiles, GEMM_NT_P8_256 = 256 x 256 tiles;
 P8_SHAPES = [(256, 256, 128),      # one tile, the shortest pipeline (one K-tile pair: prologue + drain only)
              (512, 768, 256),      # 6 tiles, two pairs
              (392, 264, 384),      # ragged M and N edges (clamped DMA rows, predicated stores)
@@ -145,17 +147,20 @@ P8_SHAPES = [(256, 256, 128),      # one tile, the shortest pipeline (one K-tile
              (1568, 2304, 1024)]   # more tiles than a quick run has CUs busy: several rounds / persistent tile loop
 
 
-PS = 32768       # variant bit 15: persistent tiles (the next tile's first K-tiles are issued before the epilogue of the current one)
-PLAIN_TN = 1 << 19     # variant bit 19 (grouped TN): the plain phases of rounds 2-4 instead of the read-ahead phases (the next phase's fragments read under the current MFMAs)
+# GEMM_NT_PERSIST: persistent tiles (the next tile's first K-tiles are issued before the epilogue of the current one)
+# GEMM_TNG_PLAIN_PHASES (grouped TN): the plain phases of rounds 2-4 instead of the read-ahead phases (the next phase's fragments read under the current MFMAs)
 
 
-@pytest.mark.parametrize("variant", [256, 512, 768, 514, 512 + PS, 768 + PS])
+@pytest.mark.parametrize("variant", [GEMM_NT_P8, GEMM_NT_P8_224, GEMM_NT_P8_256, GEMM_NT_P8_224 | GEMM_ORDER_PLAIN, GEMM_NT_P8_224 | GEMM_NT_PERSIST, GEMM_NT_P8_256 | GEMM_NT_PERSIST])
 @pytest.mark.parametrize("M,N,K", P8_SHAPES)
 def test_gemm_nt_p8_vs_oracle(ops, variant, M, N, K):
     dtype = torch.bfloat16
     a, w, b = rnd(M, K, dtype=dtype), rnd(N, K, dtype=dtype, seed=1, scale=0.1), rnd(N, seed=2)
     da, dw, out = dev(a, dtype), dev(w, dtype), e(M, N, dtype=dtype)
     assert ops.gemm_nt_tile(da, dw, out, bias=dev(b), variant=variant) == 256      # really the new kernel, not the fall-through
+    plan = ops.gemm_nt_plan(da, dw, out, bias=dev(b), variant=variant)
+    rows = {GEMM_NT_P8_224: (224,), GEMM_NT_P8_256: (256,)}.get(variant & GEMM_NT_P8_256, (224, 256))      # GEMM_NT_P8 alone: picked per problem
+    assert plan.family == ops.GEMM_NT_FAMILY_P8 and plan.tile_m in rows and (plan.persistent or not variant & GEMM_NT_PERSIST)
     ops.gemm_nt(da, dw, out, bias=dev(b), variant=variant)
     assert rel_err(out.float().cpu(), a @ w.t() + b) < TOL[dtype]
 
@@ -165,14 +170,14 @@ def test_gemm_nt_p8_asymmetric_identity(ops):
     M = N = K = 512
     w = ((torch.arange(N)[:, None] * 3 + torch.arange(K)[None, :]) % 251).float()     # exact in bf16, no two rows alike
     a = torch.eye(M)
-    for variant in (512, 768):
+    for variant in (GEMM_NT_P8_224, GEMM_NT_P8_256):
         out = ops.gemm_nt(dev(a, torch.bfloat16), dev(w, torch.bfloat16), e(M, N), variant=variant)
         assert torch.equal(out.cpu(), w.t().contiguous()), variant
 
 
 @pytest.mark.parametrize("M,N,K", P8_SHAPES)
 def test_gemm_nt_p8_bit_identical_to_128_wide_kernels(ops, M, N, K):
-    """same k order of accumulation as the 128-wide kernels -> every epilogue bit-identical (variant 1024 forbids the new kernel);
+    """same k order of accumulation as the 128-wide kernels -> every epilogue bit-identical (GEMM_NT_NO_P8 forbids the new kernel);
     repeated launches screen the counted-wait pipeline for races (a stale or half-landed LDS tile shows up as a mismatch)"""
     dtype, rps = torch.bfloat16, 196
     a, w, b = dev(rnd(M, K, dtype=dtype), dtype), dev(rnd(N, K, dtype=dtype, seed=1, scale=0.1), dtype), dev(rnd(N, seed=2))
@@ -189,10 +194,12 @@ def test_gemm_nt_p8_bit_identical_to_128_wide_kernels(ops, M, N, K):
         h2 = ops.gemm_nt(a, w, e(M, N, dtype=dtype), epi=ops.EPI_BIAS_GELU_DG, bias=b, aux=dg, variant=v)
         mu = ops.gemm_nt(a, w, e(M, N, dtype=dtype), epi=ops.EPI_MUL, aux=uu, variant=v)
         return u, h, r, d, f, dg, h2, mu
-    ref = run(1024)
-    assert ops.gemm_nt_tile(a, w, e(M, N, dtype=dtype), bias=b, variant=1024) == 128
-    NT_, SC1, PLAIN = 1 << 20, 2 << 20, 3 << 20          # store policy of the epilogue: nt / sc1 (write-through) / plain stores (0 = picked per epilogue)
-    for v in (512, 768, 512 + PS, 768 + PS, 512 + NT_, 512 + SC1, 512 + PLAIN, 512 + PS + NT_, 512 + PS + SC1, 512 + PS + PLAIN):
+    ref = run(GEMM_NT_NO_P8)
+    assert ops.gemm_nt_tile(a, w, e(M, N, dtype=dtype), bias=b, variant=GEMM_NT_NO_P8) == 128
+    # GEMM_STORE_*: store policy of the epilogue: nt / sc1 (write-through) / plain stores (0 = picked per epilogue)
+    P224, PS = GEMM_NT_P8_224, GEMM_NT_PERSIST
+    for v in (P224, GEMM_NT_P8_256, P224 | PS, GEMM_NT_P8_256 | PS, P224 | GEMM_STORE_NT, P224 | GEMM_STORE_SC1, P224 | GEMM_STORE_PLAIN,
+              P224 | PS | GEMM_STORE_NT, P224 | PS | GEMM_STORE_SC1, P224 | PS | GEMM_STORE_PLAIN):
         for rep in range(4):
             for x, y in zip(ref, run(v)):
                 assert torch.equal(x, y), (v, rep)
@@ -205,8 +212,8 @@ def test_gemm_nt_p8_vit_l_shapes_race_screen(ops):
     dtype = torch.bfloat16
     for (N, K) in [(3 * C, C), (C, C), (4 * C, C), (C, 4 * C), (C, 3 * C)]:
         a, w, b = dev(rnd(T, K, dtype=dtype), dtype), dev(rnd(N, K, dtype=dtype, seed=1, scale=0.05), dtype), dev(rnd(N, seed=2))
-        ref = ops.gemm_nt(a, w, e(T, N, dtype=dtype), bias=b, variant=1024)
-        for v in (512, 768, 512 + PS, 768 + PS):
+        ref = ops.gemm_nt(a, w, e(T, N, dtype=dtype), bias=b, variant=GEMM_NT_NO_P8)
+        for v in (GEMM_NT_P8_224, GEMM_NT_P8_256, GEMM_NT_P8_224 | GEMM_NT_PERSIST, GEMM_NT_P8_256 | GEMM_NT_PERSIST):
             out = e(T, N, dtype=dtype)
             for rep in range(6):
                 out.zero_()
@@ -214,8 +221,7 @@ def test_gemm_nt_p8_vit_l_shapes_race_screen(ops):
                 assert torch.equal(out, ref), (N, K, v, rep)
 
 
-# ---- the strip kernel (gemm_s8.hip, variant bit 17): 128 x 256 strips, two accumulator sets, epilogue slices under the next strip's K loop
-S8 = 1 << 17
+# ---- the strip kernel (gemm_s8.hip, GEMM_NT_STRIP): 128 x 256 strips, two accumulator sets, epilogue slices under the next strip's K loop
 # M / N off the strip grid (clamped DMA rows, masked stores), one strip, several strips per workgroup (> 256 strips), K from the minimum (11 K-tiles) up
 S8_SHAPES = [(128, 256, 704), (392, 520, 768), (1000, 264, 1024), (2048, 2304, 768), (12544, 1024, 1024), (12544, 3072, 1024), (6272, 768, 3072)]
 
@@ -225,8 +231,9 @@ def test_gemm_nt_s8_vs_oracle(ops, M, N, K):
     dtype = torch.bfloat16
     a, w, b = rnd(M, K, dtype=dtype), rnd(N, K, dtype=dtype, seed=1, scale=0.1), rnd(N, seed=2)
     da, dw, out = dev(a, dtype), dev(w, dtype), e(M, N, dtype=dtype)
-    assert ops.gemm_nt_tile(da, dw, out, bias=dev(b), variant=S8) == 64      # really the strip kernel, not a fall-through
-    ops.gemm_nt(da, dw, out, bias=dev(b), variant=S8)
+    assert ops.gemm_nt_tile(da, dw, out, bias=dev(b), variant=GEMM_NT_STRIP) == 64      # really the strip kernel, not a fall-through
+    assert ops.gemm_nt_plan(da, dw, out, bias=dev(b), variant=GEMM_NT_STRIP).family == ops.GEMM_NT_FAMILY_STRIP
+    ops.gemm_nt(da, dw, out, bias=dev(b), variant=GEMM_NT_STRIP)
     assert rel_err(out.float().cpu(), a @ w.t() + b) < TOL[dtype]
 
 
@@ -237,14 +244,14 @@ def test_gemm_nt_s8_asymmetric_identity(ops):
     w = ((torch.arange(N)[:, None] * 3 + torch.arange(K)[None, :]) % 251).float()     # exact in bf16, no two rows alike
     a = torch.eye(M)
     for dt in (torch.float32, torch.bfloat16):
-        out = ops.gemm_nt(dev(a, torch.bfloat16), dev(w, torch.bfloat16), e(M, N, dtype=dt), variant=S8)
+        out = ops.gemm_nt(dev(a, torch.bfloat16), dev(w, torch.bfloat16), e(M, N, dtype=dt), variant=GEMM_NT_STRIP)
         assert torch.equal(out.float().cpu(), w.t().contiguous()), dt
 
 
 @pytest.mark.parametrize("M,N,K", S8_SHAPES)
 def test_gemm_nt_s8_bit_identical_to_128_wide_kernels(ops, M, N, K):
     """same k order of accumulation and the same epilogue arithmetic as the 128-wide kernels -> every epilogue the strip kernel has must be
-    bit-identical (variant 1024 forbids the pipelined kernels); repeated launches screen the counted-wait pipeline and the in-flight
+    bit-identical (GEMM_NT_NO_P8 forbids the pipelined kernels); repeated launches screen the counted-wait pipeline and the in-flight
     side loads for races (a stale LDS tile, a side register read before its load landed or a slice of the wrong strip is a mismatch)"""
     dtype, rps = torch.bfloat16, 196
     a, w, b = dev(rnd(M, K, dtype=dtype), dtype), dev(rnd(N, K, dtype=dtype, seed=1, scale=0.1), dtype), dev(rnd(N, seed=2))
@@ -263,13 +270,13 @@ def test_gemm_nt_s8_bit_identical_to_128_wide_kernels(ops, M, N, K):
         mu = ops.gemm_nt(a, w, e(M, N, dtype=dtype), epi=ops.EPI_MUL, aux=uu, variant=v)
         rn = ops.gemm_nt(a, w, e(M, N), epi=ops.EPI_BIAS_RES, res=res, variant=v)      # residual without a bias: InternImage's data-gradient GEMMs (round 6)
         return r, r0, f, f0, y, y0, dg, h2, mu, rn
-    ref = run(1024)
-    assert ops.gemm_nt_tile(a, w, e(M, N), epi=ops.EPI_BIAS_RES, res=res, variant=S8) == 64
-    assert ops.gemm_nt_tile(a, w, e(M, N, dtype=dtype), bias=b, variant=S8) == 64
-    assert ops.gemm_nt_tile(a, w, e(M, N, dtype=dtype), epi=ops.EPI_MUL, aux=uu, variant=S8) == 64
-    assert ops.gemm_nt_tile(a, w, e(M, N), epi=ops.EPI_BIAS_RES, bias=b, res=res, rowscale=rs, rows_per_sample=rps, variant=S8) == 64
+    ref = run(GEMM_NT_NO_P8)
+    assert ops.gemm_nt_tile(a, w, e(M, N), epi=ops.EPI_BIAS_RES, res=res, variant=GEMM_NT_STRIP) == 64
+    assert ops.gemm_nt_tile(a, w, e(M, N, dtype=dtype), bias=b, variant=GEMM_NT_STRIP) == 64
+    assert ops.gemm_nt_tile(a, w, e(M, N, dtype=dtype), epi=ops.EPI_MUL, aux=uu, variant=GEMM_NT_STRIP) == 64
+    assert ops.gemm_nt_tile(a, w, e(M, N), epi=ops.EPI_BIAS_RES, bias=b, res=res, rowscale=rs, rows_per_sample=rps, variant=GEMM_NT_STRIP) == 64
     names = ("res+rowscale", "res", "f32 bias", "f32", "bf16 bias", "bf16", "gelu' out", "gelu out", "mul", "res, no bias")
-    for v in (S8, S8 + 2):
+    for v in (GEMM_NT_STRIP, GEMM_NT_STRIP | GEMM_ORDER_PLAIN):
         for rep in range(3):
             for nm, x, y in zip(names, ref, run(v)):
                 assert torch.equal(x, y), (nm, v, rep, (x.float() - y.float()).abs().max().item())
@@ -281,17 +288,17 @@ def test_gemm_nt_s8_bias_mod_and_fallbacks(ops):
     dtype = torch.bfloat16
     M, N, K, C = 512, 1024, 768, 256
     a, w, b = dev(rnd(M, K, dtype=dtype), dtype), dev(rnd(N, K, dtype=dtype, seed=1, scale=0.1), dtype), dev(rnd(C, seed=2))
-    ref = ops.gemm_nt(a, w, e(M, N, dtype=dtype), bias=b, bias_mod=C, variant=1024)
-    out = ops.gemm_nt(a, w, e(M, N, dtype=dtype), bias=b, bias_mod=C, variant=S8)
-    assert ops.gemm_nt_tile(a, w, e(M, N, dtype=dtype), bias=b, bias_mod=C, variant=S8) == 64 and torch.equal(out, ref)
+    ref = ops.gemm_nt(a, w, e(M, N, dtype=dtype), bias=b, bias_mod=C, variant=GEMM_NT_NO_P8)
+    out = ops.gemm_nt(a, w, e(M, N, dtype=dtype), bias=b, bias_mod=C, variant=GEMM_NT_STRIP)
+    assert ops.gemm_nt_tile(a, w, e(M, N, dtype=dtype), bias=b, bias_mod=C, variant=GEMM_NT_STRIP) == 64 and torch.equal(out, ref)
     a2 = dev(rnd(M, 512, dtype=dtype), dtype)
     w2 = dev(rnd(N, 512, dtype=dtype, seed=1), dtype)
-    assert ops.gemm_nt_tile(a2, w2, e(M, N, dtype=dtype), variant=S8) != 64
+    assert ops.gemm_nt_tile(a2, w2, e(M, N, dtype=dtype), variant=GEMM_NT_STRIP) != 64
     res = dev(rnd(128, N, seed=3))
     bn = dev(rnd(N, seed=4))
-    assert ops.gemm_nt_tile(a, w, e(M, N), epi=ops.EPI_BIAS_RES, bias=bn, res=res, res_mod=128, variant=S8) != 64
-    r1 = ops.gemm_nt(a, w, e(M, N), epi=ops.EPI_BIAS_RES, bias=bn, res=res, res_mod=128, variant=S8)
-    r2 = ops.gemm_nt(a, w, e(M, N), epi=ops.EPI_BIAS_RES, bias=bn, res=res, res_mod=128, variant=1024)
+    assert ops.gemm_nt_tile(a, w, e(M, N), epi=ops.EPI_BIAS_RES, bias=bn, res=res, res_mod=128, variant=GEMM_NT_STRIP) != 64
+    r1 = ops.gemm_nt(a, w, e(M, N), epi=ops.EPI_BIAS_RES, bias=bn, res=res, res_mod=128, variant=GEMM_NT_STRIP)
+    r2 = ops.gemm_nt(a, w, e(M, N), epi=ops.EPI_BIAS_RES, bias=bn, res=res, res_mod=128, variant=GEMM_NT_NO_P8)
     assert torch.equal(r1, r2)
 
 
@@ -302,11 +309,11 @@ def test_gemm_nt_s8_vit_l_shapes_race_screen(ops):
     dtype = torch.bfloat16
     for (N, K) in [(3 * C, C), (C, C), (4 * C, C), (C, 4 * C)]:
         a, w, b = dev(rnd(T, K, dtype=dtype), dtype), dev(rnd(N, K, dtype=dtype, seed=1, scale=0.05), dtype), dev(rnd(N, seed=2))
-        ref = ops.gemm_nt(a, w, e(T, N, dtype=dtype), bias=b, variant=1024)
+        ref = ops.gemm_nt(a, w, e(T, N, dtype=dtype), bias=b, variant=GEMM_NT_NO_P8)
         out = e(T, N, dtype=dtype)
         for rep in range(6):
             out.zero_()
-            ops.gemm_nt(a, w, out, bias=b, variant=S8)
+            ops.gemm_nt(a, w, out, bias=b, variant=GEMM_NT_STRIP)
             assert torch.equal(out, ref), (N, K, rep)
 
 
@@ -353,7 +360,7 @@ def _wgrad_group(ops, shapes, seed=0):
     [(128, 256, 256, True)],                                                                  # one tile, one K-tile pair
     [(256, 512, 256, True), (384, 256, 768, False), (1024, 256, 256, True)],                   # different contractions in one launch
     [(1536, 768, 256, True), (1536, 256, 256, True), (1536, 1024, 256, False), (1536, 256, 1024, True)]])   # a block's four gradients
-@pytest.mark.parametrize("variant", [0, PLAIN_TN])   # the 8-wave 8-phase kernel, read-ahead and plain phases (the 4-wave 32x32x16 form of round 3 lives in tools/ablation/)
+@pytest.mark.parametrize("variant", [0, GEMM_TNG_PLAIN_PHASES])   # the 8-wave 8-phase kernel, read-ahead and plain phases (the 4-wave 32x32x16 form of round 3 lives in tools/ablation/)
 def test_gemm_tn_grouped_vs_oracle(ops, shapes, variant):
     q, refs = _wgrad_group(ops, shapes)
     q.variant = variant
@@ -370,7 +377,7 @@ def test_gemm_tn_grouped_vs_oracle(ops, shapes, variant):
     [(512, 96, 32, True), (256, 8, 8, True), (128, 264, 520, True)],                           # narrower than one half tile; 1-chunk problem; tiles 2 x 3 with both edges
     [(16384, 192, 192, True), (16384, 384, 216, True), (32768, 96, 32, False)],                # long contractions: cut into pieces inside the launch
     [(16384 + 128, 192, 384, True)]])                                                          # ... whose last piece is shorter
-@pytest.mark.parametrize("variant", [0, PLAIN_TN])
+@pytest.mark.parametrize("variant", [0, GEMM_TNG_PLAIN_PHASES])
 def test_gemm_tn_grouped_edge_tiles_and_pieces(ops, shapes, variant):
     """sizes off the 256 grid (multiples of 8: the last tile row / column is clamped on the way in and masked on the way out) and few-tile
     problems with a long contraction (ops.grouped_splits: pieces of ~4096 rows, each an own workgroup, summed by one reduction launch)"""
@@ -384,7 +391,7 @@ def test_gemm_tn_grouped_edge_tiles_and_pieces(ops, shapes, variant):
             assert rel_err(cs.cpu(), cs0 + a.float().sum(0)) < 1e-4
 
 
-@pytest.mark.parametrize("variant", [0, PLAIN_TN])
+@pytest.mark.parametrize("variant", [0, GEMM_TNG_PLAIN_PHASES])
 def test_gemm_tn_grouped_vit_l_block_repeatable(ops, variant):
     """the four weight gradients of a ViT-L block at the training size (T = 12544 tokens, 192 tiles, 98 K-tile pairs each) against
     the split-K kernels of gemm.hip, and launch-to-launch bit-identical (no atomics on dW; one atomic per bias-gradient entry):
@@ -412,7 +419,7 @@ def test_gemm_tn_grouped_vit_l_block_repeatable(ops, variant):
         else:
             for (x, xc), (y, yc) in zip(first, outs):
                 assert torch.equal(x, y), rep
-                if variant in (0, PLAIN_TN):
+                if variant in (0, GEMM_TNG_PLAIN_PHASES):
                     assert torch.equal(xc, yc), rep
                 else:      # the 4-wave form spreads the bias gradient over the tile row: tiles_n f32 atomics per entry, order not fixed
                     assert rel_err(xc, yc) < 1e-6, rep

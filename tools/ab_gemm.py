@@ -1,4 +1,4 @@
-"""A/B of the NT GEMM kernel families / variants on the ViT-L training shapes (variant bits: include/mtp_hip.h).
+"""A/B of the NT GEMM kernel families / variants on the ViT-L training shapes (enum mtp_gemm_variant in include/mtp_hip.h, ops.GEMM_*).
 Interleaved rounds in ONE process (guide rule 24), random operands (rule 25), every variant checked bit for bit against the
 128-wide kernels.  usage: python tools/ab_gemm.py [rounds] [variant ...]"""
 import os
@@ -13,9 +13,11 @@ from mtp_amd import ops
 from tools.bench_ops import r
 
 T, C = 12544, 1024
-NT_, SC1, PLAIN = 1 << 20, 2 << 20, 3 << 20
-S8 = 1 << 17
-NAMES = {S8: "s8-strip", -1: "hipBLASLt(torch.addmm)",  512 + NT_: "p8-224-nt", 512 + SC1: "p8-224-sc1", 512 + PLAIN: "p8-224-plain", 512 + 65536: "p8-224-oneshot", 1024: "w128", 256 + 32768: "p8-persist", 512 + 32768: "p8-224-persist", 768 + 32768: "p8-256-persist", 512 + 65536: "p8-224-oneshot", 768 + 65536: "p8-256-oneshot", 256: "p8-auto", 512: "p8-224", 768: "p8-256", 258: "p8-plain"}
+P8, P224, P256, PERSIST, ONESHOT = ops.GEMM_NT_P8, ops.GEMM_NT_P8_224, ops.GEMM_NT_P8_256, ops.GEMM_NT_PERSIST, ops.GEMM_NT_NO_PERSIST
+NAMES = {ops.GEMM_NT_STRIP: "s8-strip", -1: "hipBLASLt(torch.addmm)", P224 | ops.GEMM_STORE_NT: "p8-224-nt", P224 | ops.GEMM_STORE_SC1: "p8-224-sc1",
+         P224 | ops.GEMM_STORE_PLAIN: "p8-224-plain", ops.GEMM_NT_NO_P8: "w128", P8 | PERSIST: "p8-persist", P224 | PERSIST: "p8-224-persist",
+         P256 | PERSIST: "p8-256-persist", P224 | ONESHOT: "p8-224-oneshot", P256 | ONESHOT: "p8-256-oneshot", P8: "p8-auto", P224: "p8-224", P256: "p8-256",
+         P8 | ops.GEMM_ORDER_PLAIN: "p8-plain"}
 
 
 def time_many(fn, iters):
@@ -30,7 +32,7 @@ def time_many(fn, iters):
 
 def main():
     rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-    variants = [int(v) for v in sys.argv[2:]] or [1024, 512, 768]
+    variants = [int(v) for v in sys.argv[2:]] or [ops.GEMM_NT_NO_P8, P224, P256]
     bf = torch.bfloat16
     cases = []
     shapes = [(T, 3 * C, C), (T, C, C), (T, 4 * C, C), (T, C, 4 * C), (T, C, 3 * C), (4 * T, 4 * C, C), (T, C, 768)]
@@ -74,7 +76,7 @@ def main():
             if auxs[i] is not None:
                 k2["aux"] = auxs[i]
             ops.gemm_nt(a, w, outs[i], variant=v, **k2)
-        ops.gemm_nt(a, w, ref, variant=1024, **kw)
+        ops.gemm_nt(a, w, ref, variant=ops.GEMM_NT_NO_P8, **kw)
         ts = {v: [] for v in variants}
         okv = {}
         iters = 10 if M > T else 20
@@ -84,9 +86,9 @@ def main():
                     okv[v] = True
                     time_many(lambda: launch(v), 3)
                 continue
-            if v == S8 and epi in ("gelu", "dgelu"):
+            if v == ops.GEMM_NT_STRIP and epi in ("gelu", "dgelu"):
                 continue
-            if v not in (S8, 1024, 256, 512, 768, 258, 256 + 32768, 512 + 32768, 768 + 32768, 512 + 65536, 768 + 65536, 512 + NT_, 512 + SC1, 512 + PLAIN) and epi != "bias":
+            if v not in NAMES and epi != "bias":
                 continue
             out.zero_()
             ops.gemm_nt(a, w, out, variant=v, **kw)

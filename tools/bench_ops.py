@@ -33,7 +33,7 @@ def main():
             for (M, N, K) in [(T, 3 * C, C), (T, C, C), (T, 4 * C, C), (T, C, 4 * C)]:
                 a, w, out = r(M, K, dtype=dt), r(N, K, dtype=dt, scale=0.02), torch.empty(M, N, device=dev, dtype=dt)
                 bias = torch.zeros(N, device=dev)
-                for variant in (0, 1):
+                for variant in (0, ops.GEMM_NT_REG_STAGED):
                     t = timeit(lambda: ops.gemm_nt(a, w, out, bias=bias, variant=variant))
                     print("gemm_nt %s v%d M=%d N=%d K=%d: %.3f ms  %.1f TF/s" % (str(dt)[6:], variant, M, N, K, t * 1e3, 2 * M * N * K / t / 1e12), flush=True)
             a, w = r(T, C), r(4 * C, C, scale=0.02)

@@ -1,5 +1,5 @@
 """A/B of the NT kernel families on mid-size problems (InternImage-XL levels 2 / 3: 48-128 tiles of 256 x 256 for 256 CUs): the 128-wide kernels of
-gemm.hip (variant 1024 = never the 8-phase kernel) against the 8-phase kernel forced (256 = tile height picked, 512 = 224 rows, 768 = 256 rows).
+gemm.hip (ops.GEMM_NT_NO_P8 = never the 8-phase kernel) against the 8-phase kernel forced (GEMM_NT_P8 = tile height picked, GEMM_NT_P8_224 = 224 rows, GEMM_NT_P8_256 = 256 rows).
 usage: python tools/probes/ab_gemm_mid.py [rounds]"""
 import os
 import statistics
@@ -23,10 +23,10 @@ def main():
         bias = torch.randn(N, device="cuda")
         outs = [torch.empty(M, N, device="cuda", dtype=bf) for _ in range(4)]
         ref = torch.empty(M, N, device="cuda", dtype=bf)
-        ops.gemm_nt(a, w, ref, bias=bias, variant=1024)
+        ops.gemm_nt(a, w, ref, bias=bias, variant=ops.GEMM_NT_NO_P8)
         ts, ok = {}, {}
         C2 = 1 << 22      # the co-resident 4-wave form (tools/ablation/gemm_c2.hip): only in an ablation build (MTP_HIP_LIB=tools/_abl/libmtp_hip_c2.so)
-        for v in (0, 1024, 256, 512, 768) + ((C2,) if os.environ.get("MTP_AB_C2") else ()):
+        for v in (0, ops.GEMM_NT_NO_P8, ops.GEMM_NT_P8, ops.GEMM_NT_P8_224, ops.GEMM_NT_P8_256) + ((C2,) if os.environ.get("MTP_AB_C2") else ()):
             try:
                 ops.gemm_nt(a, w, outs[0], bias=bias, variant=v)
             except Exception as e:
@@ -44,7 +44,7 @@ def main():
             for v in ts:
                 ts[v].append(time_many(lambda: (ops.gemm_nt(a, w, outs[0], bias=bias, variant=v)), 20))
         fl = 2.0 * M * N * K
-        names = {0: "default", 1024: "128-wide", 256: "p8-auto", 512: "p8-224", 768: "p8-256", 1 << 22: "c2-256x128"}
+        names = {0: "default", ops.GEMM_NT_NO_P8: "128-wide", ops.GEMM_NT_P8: "p8-auto", ops.GEMM_NT_P8_224: "p8-224", ops.GEMM_NT_P8_256: "p8-256", C2: "c2-256x128"}
         print("M=%d N=%d K=%d tiles256=%d | " % (M, N, K, -(-M // 256) * -(-N // 256)) +
               " | ".join("%s %.1fus %.0fTF%s" % (names[v], min(ts[v]) * 1e6, fl / statistics.median(ts[v]) / 1e12, ok[v]) for v in ts), flush=True)
 

@@ -50,7 +50,7 @@ def main():
                     k2 = dict(kw)
                     if epi_name != "bias_bf16":
                         k2["res"] = res[i[0]]
-                    ops.gemm_nt(a, w, outs[i[0]], variant=512, **k2)
+                    ops.gemm_nt(a, w, outs[i[0]], variant=ops.GEMM_NT_P8_224, **k2)
                 ts.append((K, timed(run)))
             n = len(ts)
             sx, sy = sum(k for k, _ in ts), sum(t for _, t in ts)
