@@ -15,6 +15,7 @@ import os
 import torch
 
 from . import ops
+from .engine_base import EngineBase
 
 F32 = torch.float32
 
@@ -24,10 +25,9 @@ class _Blk:
     __slots__ = ("window", "pre", "wqkv", "wqkvT", "wproj", "wprojT", "w1", "w1T", "w2", "w2T", "wsamp", "bsamp", "bproj", "b2", "wproj_s", "w2_s")
 
 
-class BackboneEngine:
+class BackboneEngine(EngineBase):
     def __init__(self, module, act_dtype=torch.bfloat16):
-        self.m = module
-        self.act = act_dtype
+        super().__init__(module, act_dtype)
         self.C = module.embed_dim
         self.depth = len(module.blocks)
         self.heads = module.num_heads
@@ -35,37 +35,16 @@ class BackboneEngine:
         self.scale = module.qk_scale if module.qk_scale is not None else self.hd ** -0.5
         self.window = [bool(w) for w in module.window_blocks]
         self.out_indices = list(module.out_indices)
-        self._key = None
-        self._ln_parts = []
-        self._sl_jobs = []
         self._blk = None
         self._fpn = None
         self._pe = None
-        self._wimg = None
-        self._wimg_ptrs = None
         self._ls = []
         self._zero_rel = {}
 
-    # ------------------------------------------------------------------ parameters
-    def params(self):
-        """name -> nn.Parameter (reference state-dict names)."""
-        return dict(self.m.named_parameters())
-
-    def _weights_key(self, P):
-        return (self.act,) + tuple((p.data_ptr(), p._version) for p in P.values())
-
-    def prepare_weights(self, force=False):
-        """Refresh the GEMM-side weight images when a parameter changed: ACT-dtype copies (W) and transposes (W^T) for the
-        dgrad GEMMs, the three RVSA 1x1-conv heads stacked -- ONE launch over a descriptor table (ops.WeightImages) into
-        persistent buffers; ConvTranspose2d weights as (4C, C) GEMM matrices (3 small launches)."""
-        P = self.params()
-        key = self._weights_key(P)
-        if not force and key == self._key:
-            return
-        ptrs = (self.act,) + tuple(p.data_ptr() for p in P.values())
-        if self._wimg is None or ptrs != self._wimg_ptrs:
-            self._build_weight_images(P)
-            self._wimg_ptrs = ptrs
+    # ------------------------------------------------------------------ parameters (EngineBase.prepare_weights)
+    # The weight images: ACT-dtype copies (W) and transposes (W^T) for the dgrad GEMMs, the three RVSA 1x1-conv heads stacked; behind them the
+    # ConvTranspose2d weights as (4C, C) GEMM matrices (3 small launches).
+    def _fold_sources(self, P):
         with torch.no_grad():
             for pre, b in self._ls:       # layer scale folded into the sources of the proj / fc2 images and their biases
                 g1, g2 = P[pre + "gamma_1"].detach(), P[pre + "gamma_2"].detach()
@@ -73,20 +52,13 @@ class BackboneEngine:
                 torch.mul(P[pre + "mlp.fc2.weight"].detach(), g2[:, None], out=b.w2_s)
                 torch.mul(P[pre + "attn.proj.bias"].detach(), g1, out=b.bproj)
                 torch.mul(P[pre + "mlp.fc2.bias"].detach(), g2, out=b.b2)
-        # (the optimizer launch of DataParallelTrainer writes the images itself and says so: mark_images_fresh -- honoured only while no parameter has been
-        #  touched through torch since, i.e. the version counters still are what they were then)
-        if force or getattr(self, "_images_fresh", None) != key:
-            self._wimg.refresh()
-        self._images_fresh = None
+
+    def _pack_weights(self, P):
         for name, (wg, wgT) in self._fpn.items():
             ops.convt_pack(P[name + ".weight"].detach().contiguous(), wg, wgT)
-        self._key = key
 
-    def mark_images_fresh(self):
-        """the GEMM-side weight images have just been written from the current parameters by somebody else (mtp_adamw_weight_images): the next
-        prepare_weights() skips its own image launch -- unless a parameter is modified through torch in between"""
-        self._images_fresh = self._weights_key(self.params())
-        self._key = None
+    def fusable_images(self):
+        return None if self._ls else self._wimg      # (the folded images are not plain copies of parameters)
 
     def _build_weight_images(self, P):
         dev = P["patch_embed.proj.weight"].device
@@ -155,35 +127,6 @@ class BackboneEngine:
                                   # 35.51 -> 35.25 ms on one box; one block per burst the same, three blocks worse
     wgrad_keep = 2                # bursts that may stay in flight on the side stream when the next one is launched
 
-    def _wgrad_stream(self):
-        if not self.wgrad_side_stream:
-            return None
-        import mtp_amd
-        note = mtp_amd.hw_queue_note()        # once per process: the side stream needs a hardware queue of its own (mtp_amd/__init__.py)
-        if note:
-            import warnings
-            warnings.warn(note, RuntimeWarning, stacklevel=2)
-        if int(self.wgrad_side_stream) == 2:      # a stream of the device's lowest priority
-            return ops.low_priority_stream(self.dev)
-        st = getattr(self, "_wstream", None)
-        if st is None or st.device != self.dev:
-            st = self._wstream = torch.cuda.Stream(device=self.dev)
-        return st
-
-    def warm_streams(self, device):
-        """create AND use the weight-gradient side stream now: the HIP runtime hands a stream its hardware queue at first use, in the order of first uses.  A library
-        that creates streams of its own in between (RCCL at communicator creation) otherwise pushes the side stream onto the compute stream's queue -- measured in
-        round 6: 34.6 -> 47 ms per step when the C-ABI communicator was created before the first backward (tools/probes/native_comm_probe.py)."""
-        self.dev = torch.device(device)
-        st = self._wgrad_stream()
-        if st is not None:
-            with torch.cuda.stream(st):
-                torch.zeros(1, device=self.dev).add_(1.0)
-            st.synchronize()
-
-    def _e(self, *shape, dtype=None):
-        return torch.empty(*shape, device=self.dev, dtype=dtype or self.act)
-
     # Bias / LayerNorm gradients ACCUMULATE into G (no per-call clearing pass: that was ~250 tiny memsets per step).
     # Contract of backward(): the gradient buffers in G are zero on entry (zeros_like in the autograd path, one memset of
     # the flat buffer per step in mtp_amd.parallel).
@@ -194,12 +137,6 @@ class BackboneEngine:
     def _ln_bwd(self, *args, **kw):
         # the dgamma / dbeta partial rows wait in self._ln_parts and are reduced once per burst of blocks (_ln_flush)
         return ops.layernorm_bwd(*args, accumulate=True, defer=self._ln_parts, **kw)
-
-    def _ln_flush(self):
-        if self._ln_parts:
-            ops.reduce_rows_deferred(self._ln_parts)
-        if self._sl_jobs:
-            ops.small_linear_dw_segments_flush(self._sl_jobs)
 
     def _full_rel(self, pre, Hp, Wp):
         """decomposed rel-pos tables of a full-attention block; zero tables for the ViTDet-style fine-tune copies, whose full
@@ -527,13 +464,8 @@ class BackboneEngine:
         C, N, T = self.C, Hp * Wp, B * Hp * Wp
         P = self.P
         self.dev = ctx["cols"].device
-        self._ln_parts = []
-        self._sl_jobs = []
         # weight gradients (FPN deconvolutions, the blocks' Linears, patch embed) are queued and launched in bursts (ops.WgradQueue)
-        self._wq = wq = ops.WgradQueue(stream=self._wgrad_stream())
-        wq.max_jobs = self.wgrad_max_jobs if wq.stream is not None else 0      # (on the current stream a burst should be whole rounds of the CUs)
-        wq.sqn = sqn
-        self.norm_covered = wq.covered
+        wq = self._begin_backward(sqn)
         if ctx["fctx"].get("taps_only"):
             dtaps = [None if d is None else ops.nchw_to_tokens((d.contiguous() if d.dtype in (F32, torch.bfloat16) else d.float().contiguous()),
                                                                self._e(T, C, dtype=F32), B, Hp, Wp, 0) for d in dfeats]
@@ -572,8 +504,6 @@ class BackboneEngine:
         dx = tapgrad[last]
         # ACT copy of the output gradient of the last block, scaled by its mlp drop-path factor
         dx_act = self._scaled_copy(dx, dps[last][1], N)
-        waiting = []     # blocks whose weight gradients are still queued: on_block_done fires once they have been launched
-        pending = []     # side-stream mode: (lowest block, launch mark) of the bursts in flight, reported once the current stream has waited for them
         for i in range(last, -1, -1):
             s = saved[i]
             if ctx["ckpt"]:
@@ -582,28 +512,14 @@ class BackboneEngine:
             prev_scale = dps[i - 1][1] if i > 0 else None
             dx, dx_act = self._block_bwd(i, s, dx, dx_act, B, Hp, Wp, dps[i], G, extra, prev_scale)
             saved[i] = None
-            waiting.append(i)
             if i == 0:      # the patch-embed weight gradient rides in the last burst (its input gradient is block 0's dx)
                 wq.add(dx_act, ctx["cols"], G["patch_embed.proj.weight"].view(C, -1), G["patch_embed.proj.bias"])
             # nothing queued (every weight gradient of the burst is already on the stream): report block by block -- the reducer
             # cuts its buckets by size, and a single report at the end would leave no backward to overlap the exchange with
             if i == 0 or wq.should_flush() or not wq.jobs or (split_last and i == 1):
-                wq.flush()
-                self._ln_flush()      # (on the current stream: behind the burst on the side stream they cost the whole gain, 35.4 -> 35.7 ms)
-                if wq.stream is None:
-                    if on_block_done is not None:
-                        on_block_done(waiting[-1])     # the lowest block of the burst: its group end covers the whole burst
-                else:
-                    pending.append((waiting[-1], wq.launched))
-                    wq.wait(keep=self.wgrad_keep)
-                    while pending and pending[0][1] <= wq.launched - len(wq.inflight):      # bursts the current stream has waited for
-                        g = pending.pop(0)[0]
-                        if on_block_done is not None:
-                            on_block_done(g)
-                waiting = []
-        wq.wait()
-        if pending and on_block_done is not None:
-            on_block_done(pending[-1][0])     # the lowest block still unreported covers the rest
+                self._burst_out(i, on_block_done)      # (blocks whose weight gradients stay queued are covered by the report of the burst they go out with)
+        self._wait_bursts()
+        self._report_pending(on_block_done)
         # ---- pos embed (the patch-embed weight gradient went out with block 0's)
         if "pos_embed" in G:
             ops.reduce_rows(dx.view(B, N * C), G["pos_embed"])

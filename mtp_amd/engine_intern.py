@@ -17,6 +17,7 @@ allocates buffers and draws the drop-path masks.
 import torch
 
 from . import ops
+from .engine_base import EngineBase
 from .ops_dcnv3 import functions as dcn
 
 F32 = torch.float32
@@ -26,15 +27,11 @@ class _Lin:
     __slots__ = ("name", "R", "C", "Rp", "w", "wt", "padded", "bias")
 
 
-class InternEngine:
+class InternEngine(EngineBase):
     def __init__(self, module, act_dtype=torch.bfloat16):
-        self.m = module
-        self.act = act_dtype
-        self._key = None
-        self._ptrs = None
+        super().__init__(module, act_dtype)
         self._lin = {}
         self._conv = {}
-        self._wimg = None
         self._padded = []
 
     # True: the grouped weight-gradient launches go to a side stream (ops.WgradQueue).  The Linear layers of the 768- / 1536-channel levels are 48-111
@@ -44,51 +41,8 @@ class InternEngine:
     wgrad_max_jobs = 0
     wgrad_keep = 3                # bursts that may stay in flight on the side stream when the next one is launched
 
-    def _wgrad_stream(self):
-        if not self.wgrad_side_stream:
-            return None
-        import mtp_amd
-        note = mtp_amd.hw_queue_note()        # once per process: the side stream needs a hardware queue of its own (mtp_amd/__init__.py)
-        if note:
-            import warnings
-            warnings.warn(note, RuntimeWarning, stacklevel=2)
-        if int(self.wgrad_side_stream) == 2:
-            return ops.low_priority_stream(self.dev)
-        st = getattr(self, "_wstream", None)
-        if st is None or st.device != self.dev:
-            st = self._wstream = torch.cuda.Stream(device=self.dev)
-        return st
-
-    def mark_images_fresh(self):
-        P = self.params()
-        self._images_fresh = (self.act,) + tuple((p.data_ptr(), p._version) for p in P.values())
-        self._key = None
-
-    def warm_streams(self, device):
-        """create and use the weight-gradient side stream now (BackboneEngine.warm_streams: hardware queues go to streams in the order of their first use)"""
-        self.dev = torch.device(device)
-        st = self._wgrad_stream()
-        if st is not None:
-            with torch.cuda.stream(st):
-                torch.zeros(1, device=self.dev).add_(1.0)
-            st.synchronize()
-
-    # ------------------------------------------------------------------ parameters -> GEMM-side images
-    def params(self):
-        return dict(self.m.named_parameters())
-
-    def prepare_weights(self):
-        P = self.params()
-        key = (self.act,) + tuple((p.data_ptr(), p._version) for p in P.values())
-        if key == self._key:
-            return
-        ptrs = (self.act,) + tuple(p.data_ptr() for p in P.values())
-        if ptrs != self._ptrs:
-            self._build(P)
-            self._ptrs = ptrs
-        if self._wimg is not None and getattr(self, "_images_fresh", None) != key:      # (BackboneEngine.mark_images_fresh: the optimizer launch wrote them)
-            self._wimg.refresh()
-        self._images_fresh = None
+    # ------------------------------------------------------------------ parameters -> GEMM-side images (EngineBase.prepare_weights)
+    def _pack_weights(self, P):
         for L in self._padded:
             ops.pack_rows_padded(P[L.name].detach(), L.w, L.wt)
         for k in range(0, len(self._padded), 12):      # the padded layers' biases: R floats each, 12 per launch
@@ -96,9 +50,8 @@ class InternEngine:
             ops.copy_segments([P[L.name[:-len("weight")] + "bias"].detach() for L in Ls], [L.bias[:L.R] for L in Ls])
         for name, (w2, w2t) in self._conv.items():
             ops.conv3x3_pack(P[name].detach().contiguous(), w2, w2t)
-        self._key = key
 
-    def _build(self, P):
+    def _build_weight_images(self, P):
         dev = next(iter(P.values())).device
         act = self.act
         entries, self._lin, self._conv, self._padded = [], {}, {}, []
@@ -130,9 +83,6 @@ class InternEngine:
         self._wimg = ops.WeightImages(entries, act) if entries else None
 
     # ------------------------------------------------------------------ helpers
-    def _e(self, *shape, dtype=None):
-        return torch.empty(*shape, device=self.dev, dtype=dtype or self.act)
-
     def _linear(self, x, wname, bias, padded_out=False, **kw):
         """x @ W^T + b.  Padded weights: the GEMM writes Rp columns; the result is compacted to R columns unless the caller reads
         it through its pitch (padded_out)."""
@@ -168,10 +118,6 @@ class InternEngine:
         ops.layernorm_bwd(dy, x, mean, rstd, P[key + ".weight"], dx, G[key + ".weight"], G[key + ".bias"],
                           beta=P[key + ".bias"] if gelu else None, gelu=gelu, accumulate=True, defer=self._ln_parts)
         return dx
-
-    def _ln_flush(self):
-        if self._ln_parts:
-            ops.reduce_rows_deferred(self._ln_parts)
 
     def _to_act(self, t):
         return t if t.dtype == self.act else ops.cast(t, self._e(*t.shape))
@@ -505,12 +451,7 @@ class InternEngine:
         P = self.P
         img, cols1, y1, sm1, sr1, a1, cols2, y2, sm2, sr2, (N, Cin, H, W, H1, W1, H2, W2) = ctx["stem"]
         self.dev = cols1.device
-        self._wq = wq = ops.WgradQueue(stream=self._wgrad_stream())
-        wq.max_jobs = self.wgrad_max_jobs if wq.stream is not None else 0
-        wq.sqn = sqn                      # the clipping step's gradient norm as a by-product of the grouped launches (BackboneEngine.backward)
-        self.norm_covered = wq.covered
-        pending = []        # side-stream mode: the layers whose bursts are in flight (reported once the current stream has waited for them)
-        self._ln_parts = []
+        wq = self._begin_backward(sqn)    # (sqn: the clipping step's gradient norm as a by-product of the grouped launches, BackboneEngine.backward)
         taps = {}
         for idx, d in zip([i for i in range(len(m.depths)) if i in m.out_indices], dfeats):
             taps[idx] = d
@@ -556,18 +497,7 @@ class InternEngine:
                 # levels and the offset / mask heads, the contraction of the 131072- / 32768-token levels cut into pieces inside the launch);
                 # the layer is reported once they are out
                 if j == 0 or wq.should_flush() or not wq.jobs:
-                    wq.flush()
-                    self._ln_flush()
-                    if wq.stream is None:
-                        if on_block_done is not None:
-                            on_block_done(sum(m.depths[:i]) + j)
-                    else:
-                        pending.append((sum(m.depths[:i]) + j, wq.launched))
-                        wq.wait(keep=self.wgrad_keep)
-                        while pending and pending[0][1] <= wq.launched - len(wq.inflight):      # bursts the current stream has waited for
-                            g = pending.pop(0)[0]
-                            if on_block_done is not None:
-                                on_block_done(g)
+                    self._burst_out(sum(m.depths[:i]) + j, on_block_done)
         if dx32 is None:
             return None
         # ---- stem backward
@@ -580,7 +510,7 @@ class InternEngine:
         self._conv_bwd(dy1, cols1, "patch_embed.conv1.weight", G, "patch_embed.conv1.bias", dimg, (Cin * H * W, W, 1, H * W), N, H, W, Cin, 2)
         wq.flush()      # the stem's two weight gradients
         self._ln_flush()
-        wq.wait()
+        self._wait_bursts()
         if on_block_done is not None:
             on_block_done(-1)
         return dimg

@@ -261,7 +261,7 @@ class GradReducer:
         self.native, self.native_error = None, None
         if self.stream is not None and os.environ.get("MTP_NATIVE_COMM", "1") != "0":
             from .comm import RcclComm
-            # (the exchange stream takes its hardware queue at first use: use it BEFORE RCCL creates the communicator's own streams -- BackboneEngine.warm_streams)
+            # (the exchange stream takes its hardware queue at first use: use it BEFORE RCCL creates the communicator's own streams -- EngineBase.warm_streams)
             with torch.cuda.stream(self.stream):
                 torch.zeros(1, device=flat.grad.device).add_(1.0)
             self.stream.synchronize()
@@ -652,7 +652,7 @@ class DataParallelTrainer:
         self.engine = module._engine()
         self.flat = FlatParams(module, unused=module._unused_params)
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-        if self.flat.data.is_cuda and hasattr(self.engine, "warm_streams"):
+        if self.flat.data.is_cuda:
             self.engine.warm_streams(self.flat.data.device)      # before the reducer creates its RCCL communicator
         self.reducer = GradReducer(self.flat, bucket_bytes, mode=comm_mode, bf16=comm_bf16)
         self.opt = FlatAdamW(self.flat, lr=lr, betas=betas, weight_decay=weight_decay, max_norm=max_norm, total_steps=total_steps, world_size=self.world,
@@ -695,8 +695,7 @@ class DataParallelTrainer:
             if self.head is not None:
                 self.hopt.t, self.hopt.last_epoch, self.hopt.total_steps, self.hopt.sched_pending = \
                     self.opt.t, self.opt.last_epoch, self.opt.total_steps, self.opt.sched_pending
-        self.engine._key = None
-        self.engine._images_fresh = None
+        self.engine.invalidate_weights()
 
     # ---- encoder checkpoint in the reference's dict format (MAIN:823-829 save, MAIN:483-499 resume) -------------------------
     def checkpoint(self, epoch=0, iteration=None, losses=()):
@@ -763,8 +762,7 @@ class DataParallelTrainer:
         if self.head is not None:       # the head's optimizer runs in lock step with the backbone's
             self.hopt.t, self.hopt.last_epoch, self.hopt.total_steps, self.hopt.sched_pending = \
                 self.opt.t, self.opt.last_epoch, self.opt.total_steps, self.opt.sched_pending
-        self.engine._key = None
-        self.engine._images_fresh = None
+        self.engine.invalidate_weights()
         self.sync_replicas(optimizer_state=True)
         losses = ckpt.get("loss_pretrain", [])
         return ckpt.get("epoch", 0), ckpt.get("iteration", self.opt.t), (losses.tolist() if hasattr(losses, "tolist") else list(losses))
@@ -782,8 +780,7 @@ class DataParallelTrainer:
                 w.wait()
         # the gradient norm of the clipping step as a by-product of the weight-gradient launches (one rank only: with an exchange the norm is that of the REDUCED
         # gradients; MTP_FUSED_SQNORM=0: always the separate pass)
-        fold = (self.world == 1 and not self.reducer.active and self.flat.grad.is_cuda and bool(self.opt.max_norm) and os.environ.get("MTP_FUSED_SQNORM", "1") != "0"
-                and "sqn" in self.engine.backward.__code__.co_varnames)
+        fold = (self.world == 1 and not self.reducer.active and self.flat.grad.is_cuda and bool(self.opt.max_norm) and os.environ.get("MTP_FUSED_SQNORM", "1") != "0")
         kw = {}
         if fold:
             self.opt.sqn.zero_()
@@ -791,14 +788,14 @@ class DataParallelTrainer:
         # (split_last: with collectives in flight, block 0's weight gradients go out on their own so that only ~50 MB stay exposed)
         self.engine.backward(ctx, dfeats, self.flat.G, on_block_done=self.reducer.on_block_done, split_last=self.reducer.active, **kw)
         self.reducer.finish()
-        covered = list(getattr(self.engine, "norm_covered", None) or []) if fold else None
-        wimg = getattr(self.engine, "_wimg", None)
+        covered = list(self.engine.norm_covered) if fold else None
+        wimg = self.engine.fusable_images()
         if getattr(self.opt, "_fused_for", 0) is not wimg:       # (first step, or the engine rebuilt its image buffers)
-            self.opt.fuse_images(wimg if not getattr(self.engine, "_ls", None) else None)
+            self.opt.fuse_images(wimg)
         fresh = self.opt.step(norm_covered=covered, extra_norm=(self.hflat.grad,) if self.head is not None else ())
         if self.head is not None:
             self.hopt.step(sq=self.opt.sqn if self.opt.max_norm and self.opt.max_norm > 0 else None)
-        self.engine._key = None   # parameters changed under torch's version counters: rebuild the GEMM weight images next forward ...
-        if fresh and hasattr(self.engine, "mark_images_fresh"):
+        self.engine.invalidate_weights()          # parameters changed under torch's version counters: rebuild the GEMM weight images next forward ...
+        if fresh:
             self.engine.mark_images_fresh()       # ... unless the optimizer kernel has just written them (the packed ConvT / convolution weights still follow)
         return loss
