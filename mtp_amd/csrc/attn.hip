@@ -8,12 +8,11 @@
 // phases, so no cross-lane reductions are needed on the hot loops.
 #include <stdlib.h>
 
-#include "attn_mfma.h"
-#include "common.h"
+#include "attn_launch.h"
+#include "attn_rvsa_common.h"   // HD; RvsaGeom, make_geom, make_sample, neighbour: one sampling geometry for these kernels and the MFMA ones
 
 namespace {
 
-constexpr int HD = 64;
 constexpr int KT = 32;  // keys (or queries) staged per LDS chunk in the full-attention kernels
 
 template <typename T>
@@ -450,57 +449,6 @@ __global__ __launch_bounds__(256) void full_attn_bwdN_k_kernel(const T* __restri
 }
 
 // =====================================================================================================================
-// RVSA geometry shared by forward and backward
-// =====================================================================================================================
-struct RvsaGeom {
-    int Hp, Wp, He, We, pad_t, pad_l, nh, nw, heads;
-    float inv_div_x, inv_div_y;
-};
-
-struct Sample {         // one key position's sampling footprint
-    float ix, iy, fx, fy;
-    int x0, y0;
-    float rx, ry, cs, sn, relx, rely;
-};
-
-__device__ __forceinline__ Sample make_sample(const RvsaGeom& g, const float* __restrict__ sp, int h, int wi, int wj, int a, int bb) {
-    Sample s;
-    const int H = g.heads;
-    const float offx = sp[2 * h] * g.inv_div_x, offy = sp[2 * h + 1] * g.inv_div_y;
-    const float sx = sp[2 * H + 2 * h] + 1.0f, sy = sp[2 * H + 2 * h + 1] + 1.0f;
-    const float ang = sp[4 * H + h];
-    const float stepx = 2.0f / (float)(g.We - 1), stepy = 2.0f / (float)(g.He - 1);
-    const float cenx = -1.0f + stepx * (float)(7 * wj + 3), ceny = -1.0f + stepy * (float)(7 * wi + 3);   // mean of 7 linspace points
-    s.relx = (float)(bb - 3) * stepx;
-    s.rely = (float)(a - 3) * stepy;
-    s.rx = s.relx * sx;
-    s.ry = s.rely * sy;
-    s.cs = cosf(ang);
-    s.sn = sinf(ang);
-    const float gx = cenx + (s.rx * s.cs - s.ry * s.sn) + offx;
-    const float gy = ceny + (s.ry * s.cs + s.rx * s.sn) + offy;
-    float ix = (gx + 1.0f) * 0.5f * (float)(g.We - 1), iy = (gy + 1.0f) * 0.5f * (float)(g.He - 1);
-    ix = fminf(fmaxf(ix, -4.0f), (float)g.We + 4.0f);   // far-out samples contribute 0 anyway; keeps floor() in int range
-    iy = fminf(fmaxf(iy, -4.0f), (float)g.He + 4.0f);
-    s.ix = ix; s.iy = iy;
-    const float fx0 = floorf(ix), fy0 = floorf(iy);
-    s.x0 = (int)fx0; s.y0 = (int)fy0;
-    s.fx = ix - fx0; s.fy = iy - fy0;
-    return s;
-}
-// neighbour k in {0:(x0,y0), 1:(x1,y0), 2:(x0,y1), 3:(x1,y1)}: bilinear weight, and token index (or -1 when the neighbour
-// is outside the padded map [zeros padding of grid_sample] or inside the zero padding ring of the map itself)
-__device__ __forceinline__ int neighbour(const RvsaGeom& g, const Sample& s, int k, float& w, bool& in_map) {
-    const int dx = k & 1, dy = k >> 1;
-    const int xi = s.x0 + dx, yi = s.y0 + dy;
-    w = (dx ? s.fx : 1.0f - s.fx) * (dy ? s.fy : 1.0f - s.fy);
-    in_map = xi >= 0 && xi <= g.We - 1 && yi >= 0 && yi <= g.He - 1;
-    const int tx = xi - g.pad_l, ty = yi - g.pad_t;
-    if (!in_map || tx < 0 || tx >= g.Wp || ty < 0 || ty >= g.Hp) return -1;
-    return ty * g.Wp + tx;
-}
-
-// =====================================================================================================================
 // RVSA forward.  grid (B*nW*heads), 64 threads (one wave): lane = key for the gather, lane = query afterwards.
 // LDS floats: Ksel[49*64] | Vsel[49*64] | relq[14*64] | sbuf[49*64] | tab[176]
 // =====================================================================================================================
@@ -531,11 +479,11 @@ __global__ __launch_bounds__(64) void rvsa_attn_fwd_kernel(const T* __restrict__
 #pragma unroll
         for (int d = 0; d < HD; ++d) { ks[d] = 0.f; vs[d] = 0.f; q[d] = 0.f; }
         if (active) {
-            const Sample s = make_sample(g, samp + (int64_t)bw * 5 * H, h, wi, wj, a, bb);
+            const Sample s = make_sample<false>(g, samp + (int64_t)bw * 5 * H, h, wi, wj, a, bb);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                float w; bool in_map;
-                const int tok = neighbour(g, s, k, w, in_map);
+                float w;
+                const int tok = neighbour(g, s.x0, s.y0, s.fx, s.fy, k, w);
                 if (tok >= 0) {
                     float t[HD];
                     load_row(base + C + (int64_t)tok * ld, t);
@@ -629,15 +577,15 @@ __global__ __launch_bounds__(64) void rvsa_attn_bwd_kernel(const T* __restrict__
     for (int d = 0; d < HD; ++d) { q[d] = 0.f; dO[d] = 0.f; }
     float dl = 0.f, ls = 0.f;
     if (active) {
-        smp = make_sample(g, samp + (int64_t)bw * 5 * H, h, wi, wj, a, bb);
+        smp = make_sample<false>(g, samp + (int64_t)bw * 5 * H, h, wi, wj, a, bb);
         {
             float ks[HD], vs[HD];
 #pragma unroll
             for (int d = 0; d < HD; ++d) { ks[d] = 0.f; vs[d] = 0.f; }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                float w; bool in_map;
-                const int tok = neighbour(g, smp, k, w, in_map);
+                float w;
+                const int tok = neighbour(g, smp.x0, smp.y0, smp.fx, smp.fy, k, w);
                 if (tok >= 0) {
                     float t[HD];
                     load_row(base + C + (int64_t)tok * ld, t);
@@ -761,8 +709,8 @@ __global__ __launch_bounds__(64) void rvsa_attn_bwd_kernel(const T* __restrict__
     if (active) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            float w; bool in_map;
-            const int tok = neighbour(g, smp, k, w, in_map);
+            float w;
+            const int tok = neighbour(g, smp.x0, smp.y0, smp.fx, smp.fy, k, w);
             if (tok >= 0) {
                 float* dkrow = dkv + ((int64_t)b * N + tok) * (2 * C) + h * HD;
                 float t[HD];
@@ -813,19 +761,6 @@ __global__ __launch_bounds__(256) void dkv_convert_kernel(const float* __restric
     }
 }
 
-RvsaGeom make_geom(int64_t Hp, int64_t Wp, int64_t heads) {
-    RvsaGeom g;
-    const int pad_h = (int)((7 - Hp % 7) % 7), pad_w = (int)((7 - Wp % 7) % 7);
-    g.Hp = (int)Hp; g.Wp = (int)Wp;
-    g.pad_t = pad_h / 2; g.pad_l = pad_w / 2;
-    g.He = (int)Hp + pad_h; g.We = (int)Wp + pad_w;
-    g.nh = g.He / 7; g.nw = g.We / 7;
-    g.heads = (int)heads;
-    g.inv_div_x = 1.0f / (float)(Hp / 7);   // VIT:359: x offset / (h // ws)
-    g.inv_div_y = 1.0f / (float)(Wp / 7);   // VIT:360: y offset / (w // ws)
-    return g;
-}
-
 // ---- the dispatch: which kernel family takes (dtype, grid).  The entry points below launch what these name; mtp_full_attn_kernel /
 // mtp_rvsa_attn_kernel report the same value (the tests assert it per case).  bf16 I/O takes the MFMA families where one fits; f32 I/O
 // (parity mode) and the remaining grids run the f32-math kernels of this file.
@@ -834,7 +769,7 @@ size_t full_bwd3_lds_q(int64_t Hp, int64_t Wp) { return sizeof(float) * (size_t)
 size_t full_bwd1_lds(int64_t Hp, int64_t Wp) { return sizeof(float) * (size_t)(2 * (Hp + Wp) * 256 + 512 + 2 * KT * HD); }
 
 int full_fwd_family(int dtype, int64_t Hp, int64_t Wp) {
-    if (dtype == MTP_BF16 && mtp_use_mfma_attn()) {
+    if (dtype == MTP_BF16) {
         if (mtp_full_v3_fits(Hp, Wp)) return MTP_FULL_FWD_V3;
         if (mtp_full_mfma1_fits(Hp, Wp, false)) return MTP_FULL_FWD_MFMA1;
         const int keys = mtp_full_fwd_flash_keys(Hp, Wp);
@@ -844,7 +779,7 @@ int full_fwd_family(int dtype, int64_t Hp, int64_t Wp) {
 }
 
 int full_bwd_family(int dtype, int64_t Hp, int64_t Wp) {
-    if (dtype == MTP_BF16 && mtp_use_mfma_attn()) {
+    if (dtype == MTP_BF16) {
         if (mtp_full_v3_fits(Hp, Wp)) return MTP_FULL_BWD_V3;
         if (mtp_full_mfma1_fits(Hp, Wp, true)) return MTP_FULL_BWD_MFMA1;
         if (mtp_full_bwd_flash_fits(Hp, Wp)) return MTP_FULL_BWD_FLASH;
@@ -855,10 +790,10 @@ int full_bwd_family(int dtype, int64_t Hp, int64_t Wp) {
     return full_bwd1_lds(Hp, Wp) <= 160 * 1024 ? MTP_FULL_BWD_SINGLE_WG : MTP_ATTN_KERNEL_NONE;
 }
 
-int rvsa_fwd_family(int dtype) { return dtype == MTP_BF16 && mtp_use_mfma_attn() ? MTP_RVSA_FWD_MFMA : MTP_RVSA_FWD_GENERIC; }
+int rvsa_fwd_family(int dtype) { return dtype == MTP_BF16 ? MTP_RVSA_FWD_MFMA : MTP_RVSA_FWD_GENERIC; }
 
 int rvsa_bwd_family(int dtype, int64_t Hp, int64_t Wp, int64_t heads) {
-    if (!(dtype == MTP_BF16 && mtp_use_mfma_attn())) return MTP_RVSA_BWD_GENERIC;
+    if (dtype != MTP_BF16) return MTP_RVSA_BWD_GENERIC;
     return mtp_rvsa_bwd_mfma_scatter_mode(Hp, Wp, heads) == 4 ? MTP_RVSA_BWD_MFMA_DENSE : MTP_RVSA_BWD_MFMA_ATOMIC;
 }
 

@@ -1,26 +1,17 @@
 // helpers shared by the full-attention MFMA kernels (attn_full_mfma.hip: <= 256 tokens and the flash forward;
 // attn_full_flash_bwd.hip: the flash backward beyond 256 tokens).  Internal linkage: every translation unit gets its own copy.
 #pragma once
-#include "common.h"
+#include "attn_common.h"
 
 namespace {
 
-constexpr int HD = 64;
-
 __device__ __attribute__((aligned(16))) const uint4 g_zero16f = {0u, 0u, 0u, 0u};
 
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
-__device__ __forceinline__ f32x4_t mma(const uint4& a, const uint4& b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ uint4 ld16(const char* p) { return *reinterpret_cast<const uint4*>(p); }
-__device__ __forceinline__ uint4 ld8x2(const char* p0, const char* p1) {
-    const uint2 a = *reinterpret_cast<const uint2*>(p0), b = *reinterpret_cast<const uint2*>(p1);
-    return make_uint4(a.x, a.y, b.x, b.y);
-}
 __device__ __forceinline__ uint4 row_frag(const bf16_t* __restrict__ rows, int64_t ld, int tok, bool ok, int e0) {
     return ldg16(ok ? reinterpret_cast<const char*>(rows + (int64_t)tok * ld + e0) : reinterpret_cast<const char*>(&g_zero16f));
 }
+// the table operands are the BRANCHY forms (the RVSA family has clamped loads under the same names, attn_rvsa_common.h; the two headers never meet in one
+// translation unit)
 __device__ __forceinline__ uint4 table_frag(const float* __restrict__ tab, int r, int rows, int e0) {
     if (r >= rows) return make_uint4(0, 0, 0, 0);
     const float4 a = *reinterpret_cast<const float4*>(tab + r * HD + e0), b = *reinterpret_cast<const float4*>(tab + r * HD + e0 + 4);

@@ -13,7 +13,7 @@
 //          dQ^T += Rh^T.dQRh + Rw^T.dQRw and the table gradients d(rel_pos_h/w) += dQR . Q (atomics into the per-(image, head) partials)
 //   dkv  : workgroup = 64 keys, loop over blocks of 64 queries: dV^T += dO^T.P, dK^T += Q^T.dS; the bias comes from the
 //          workspace rows (only the <= 8 grid rows the workgroup's keys touch, and all Wp columns)
-#include "attn_mfma.h"
+#include "attn_launch.h"
 #include "attn_full_common.h"
 
 namespace {

@@ -2,12 +2,12 @@
 // decomposed relative-position terms of calc_rel_pos_spatial, VIT:142-193), gfx950, head_dim 64, N = Hp*Wp <= 256 tokens.
 //
 // One workgroup per (image, head) (forward: 4 waves; backward A / B: 8 waves where the LDS allows); K (row-major, XOR-swizzled) and
-// V^T (transposed image) live in LDS; each wave owns 16-query (or 16-key) tiles.  Same tricks as the RVSA kernels (attn_mfma.hip): S^T = K.Q^T so a query's softmax is
+// V^T (transposed image) live in LDS; each wave owns 16-query (or 16-key) tiles.  Same tricks as the RVSA kernels (attn_rvsa_common.h): S^T = K.Q^T so a query's softmax is
 // in-lane + two shuffles and P is directly the B operand of O^T = V^T.P^T; the q.Rh / q.Rw terms are one MFMA against the
 // tables, exchanged through a per-wave LDS tile; the backward uses both MFMA orientations instead of transposing P/dS:
 //   kernel A (lane: query, 4 keys)  : dQ^T = K^T.dS^T + Rh^T.dQRh + Rw^T.dQRw,  d(rel_pos_h/w) partials
 //   kernel B (lane: key, 4 queries) : dK^T = Q^T.dS,  dV^T = dO^T.P
-#include "attn_mfma.h"
+#include "attn_launch.h"
 #include "attn_full_common.h"
 
 namespace {

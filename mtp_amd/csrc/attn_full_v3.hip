@@ -22,7 +22,7 @@
 // Orientation tricks are the ones of attn_full_mfma.hip: S^T = K.Q^T so that a query's softmax is in-lane + two shuffles and P^T is
 // directly the B operand of O^T = V^T.P^T; the backward uses both orientations (kernel A: lane = query, dQ and the table gradients;
 // kernel B: lane = key, dK and dV).  Scale convention: logits = scale * S (VIT:100 scales q before both products).
-#include "attn_mfma.h"
+#include "attn_launch.h"
 #include "attn_full_common.h"
 
 namespace {

@@ -1,4 +1,5 @@
-// internal launchers of the bf16 MFMA attention kernels (attn_mfma.hip), called from the C-ABI entry points in attn.hip
+// internal launchers and fit predicates of the bf16 MFMA attention kernels (attn_rvsa_fwd4.hip, attn_rvsa_bwd4.hip, attn_full_mfma.hip, attn_full_v3.hip,
+// attn_full_flash_bwd.hip), called from the dispatch and the C-ABI entry points in attn.hip
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,7 +35,3 @@ int mtp_full_v3_bwd_launch(const void* qkv, const void* o, const void* dout, con
 // beyond 256 tokens (attn_full_flash_bwd.hip); workspace as mtp_full_attn_bwd_workspace_floats
 int mtp_full_bwd_flash_launch(const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv, const float* rel_h, const float* rel_w,
                               float* drel_part, float* workspace, int64_t B, int64_t Hp, int64_t Wp, int64_t heads, float scale, hipStream_t s);
-
-// bf16 I/O always takes the MFMA kernels; the f32-math VALU kernels of attn.hip serve f32 I/O (parity mode) and the grids the MFMA kernels
-// do not take
-static inline bool mtp_use_mfma_attn() { return true; }

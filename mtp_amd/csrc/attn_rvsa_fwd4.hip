@@ -1,149 +1,8 @@
-// 4-wave variant of the RVSA forward (see attn_mfma.hip for the algorithm).
-#include "attn_mfma.h"
-#include "common.h"
+// RVSA forward, 4 waves per (image, window, head) (attn_rvsa_common.h has the algorithm and the lane layout).
+#include "attn_launch.h"
+#include "attn_rvsa_common.h"
 
 namespace {
-
-constexpr int HD = 64;
-constexpr int TP = 136;   // byte pitch of the transposed [d][key|query] bf16 images (128 + 8: conflict-free 8-byte reads)
-
-struct RvsaGeom {
-    int Hp, Wp, He, We, pad_t, pad_l, nh, nw, heads;
-    float inv_div_x, inv_div_y;
-};
-struct Sample {
-    float fx, fy;
-    int x0, y0;
-    float rx, ry, cs, sn, relx, rely;
-};
-
-__device__ __forceinline__ Sample make_sample(const RvsaGeom& g, const float* __restrict__ sp, int h, int wi, int wj, int a, int bb) {
-    Sample s;
-    const int H = g.heads;
-    const float offx = sp[2 * h] * g.inv_div_x, offy = sp[2 * h + 1] * g.inv_div_y;
-    const float sx = sp[2 * H + 2 * h] + 1.0f, sy = sp[2 * H + 2 * h + 1] + 1.0f;
-    const float ang = sp[4 * H + h];
-    const float stepx = 2.0f / (float)(g.We - 1), stepy = 2.0f / (float)(g.He - 1);
-    const float cenx = -1.0f + stepx * (float)(7 * wj + 3), ceny = -1.0f + stepy * (float)(7 * wi + 3);
-    s.relx = (float)(bb - 3) * stepx;
-    s.rely = (float)(a - 3) * stepy;
-    s.rx = s.relx * sx;
-    s.ry = s.rely * sy;
-    s.cs = __cosf(ang);      // v_cos / v_sin (abs error ~1e-6 on |ang| < pi): shared with the backward kernel
-    s.sn = __sinf(ang);
-    const float gx = cenx + (s.rx * s.cs - s.ry * s.sn) + offx;
-    const float gy = ceny + (s.ry * s.cs + s.rx * s.sn) + offy;
-    float ix = (gx + 1.0f) * 0.5f * (float)(g.We - 1), iy = (gy + 1.0f) * 0.5f * (float)(g.He - 1);
-    ix = fminf(fmaxf(ix, -4.0f), (float)g.We + 4.0f);
-    iy = fminf(fmaxf(iy, -4.0f), (float)g.He + 4.0f);
-    const float fx0 = floorf(ix), fy0 = floorf(iy);
-    s.x0 = (int)fx0; s.y0 = (int)fy0;
-    s.fx = ix - fx0; s.fy = iy - fy0;
-    return s;
-}
-__device__ __forceinline__ int neighbour(const RvsaGeom& g, int x0, int y0, float fx, float fy, int k, float& w) {
-    const int dx = k & 1, dy = k >> 1;
-    const int xi = x0 + dx, yi = y0 + dy;
-    w = (dx ? fx : 1.0f - fx) * (dy ? fy : 1.0f - fy);
-    const int tx = xi - g.pad_l, ty = yi - g.pad_t;
-    if (xi < 0 || xi > g.We - 1 || yi < 0 || yi > g.He - 1 || tx < 0 || tx >= g.Wp || ty < 0 || ty >= g.Hp) return -1;
-    return ty * g.Wp + tx;
-}
-__device__ __forceinline__ int query_token(const RvsaGeom& g, int n, int wi, int wj) {   // n < 49
-    const int a = n / 7, bb = n - 7 * a;
-    const int ty = 7 * wi + a - g.pad_t, tx = 7 * wj + bb - g.pad_l;
-    return (ty >= 0 && ty < g.Hp && tx >= 0 && tx < g.Wp) ? ty * g.Wp + tx : -1;
-}
-
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
-__device__ __forceinline__ f32x4_t mma(const uint4& a, const uint4& b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ uint4 ld16(const char* p) { return *reinterpret_cast<const uint4*>(p); }
-__device__ __forceinline__ uint4 ld8x2(const char* p0, const char* p1) {   // two 8-byte LDS reads -> one 8 x bf16 operand
-    const uint2 a = *reinterpret_cast<const uint2*>(p0), b = *reinterpret_cast<const uint2*>(p1);
-    return make_uint4(a.x, a.y, b.x, b.y);
-}
-// 8 f32 table values (row r, elements e0..e0+7) -> bf16 operand; zero when the row is out of range
-__device__ __forceinline__ uint4 table_frag(const float* __restrict__ tab, int r, int rows, int e0) {
-    // unconditional loads on a clamped row, masked afterwards: a branch around the loads makes hipcc wait for them inside it
-    const int rc = r < rows ? r : rows - 1;
-    const float m = r < rows ? 1.0f : 0.0f;
-    const float4 a = *reinterpret_cast<const float4*>(tab + rc * HD + e0), b = *reinterpret_cast<const float4*>(tab + rc * HD + e0 + 4);
-    return pack_bf16x8(m * a.x, m * a.y, m * a.z, m * a.w, m * b.x, m * b.y, m * b.z, m * b.w);
-}
-// transposed table operand: lane (d, g) -> tab[8g+e][d], e = 0..7
-__device__ __forceinline__ uint4 table_frag_t(const float* __restrict__ tab, int d, int rows, int r0) {
-    float v[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {      // unconditional loads on clamped rows (see table_frag)
-        const int r = r0 + e;
-        const float t = tab[(r < rows ? r : rows - 1) * HD + d];
-        v[e] = r < rows ? t : 0.f;
-    }
-    return pack_bf16x8(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
-}
-
-// lane = key: bilinear gather of this key's K/V rows (f32 blend of <= 4 bf16 token rows)
-__device__ __forceinline__ void gather_kv(const RvsaGeom& g, const Sample& s, const bf16_t* __restrict__ base, int64_t ld, int C, float (&ks)[HD], float (&vs)[HD]) {
-    // branch-free: an out-of-map neighbour reads token 0 with weight 0 (a branch around the loads would make hipcc wait for
-    // every neighbour separately; this way all 64 row loads are in flight together)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        float w;
-        const int tok = neighbour(g, s.x0, s.y0, s.fx, s.fy, k, w);
-        const int tc = tok >= 0 ? tok : 0;
-        w = tok >= 0 ? w : 0.f;
-#pragma unroll
-        for (int i = 0; i < HD / 8; ++i) {
-            float t[8];
-            load8(base + C + (int64_t)tc * ld + 8 * i, t);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) ks[8 * i + e] += w * t[e];
-            load8(base + 2 * C + (int64_t)tc * ld + 8 * i, t);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) vs[8 * i + e] += w * t[e];
-        }
-    }
-}
-__device__ __attribute__((aligned(16))) const uint4 g_zero16a = {0u, 0u, 0u, 0u};
-// 16-byte fragment of row `tok` (or zeros when tok < 0) without a branch around the load
-__device__ __forceinline__ uint4 row_frag(const bf16_t* __restrict__ rows, int64_t ld, int tok, int e0) {
-    return ldg16(tok >= 0 ? reinterpret_cast<const char*>(rows + (int64_t)tok * ld + e0) : reinterpret_cast<const char*>(&g_zero16a));
-}
-__device__ __forceinline__ void put_row_swz(char* img, int row, const float (&v)[HD]) {
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-        *reinterpret_cast<uint4*>(img + swz(row, c)) = pack_bf16x8(v[8 * c], v[8 * c + 1], v[8 * c + 2], v[8 * c + 3], v[8 * c + 4], v[8 * c + 5], v[8 * c + 6], v[8 * c + 7]);
-}
-__device__ __forceinline__ void put_col_t(char* img, int col, const float (&v)[HD]) {   // img[d][col] = v[d]
-#pragma unroll
-    for (int d = 0; d < HD; ++d) *reinterpret_cast<uint16_t*>(img + d * TP + col * 2) = (uint16_t)f32_to_bf16_bits(v[d]);
-}
-__device__ __forceinline__ void put_col_t_bits(char* img, int col, const uint4 (&rowbits)[8]) {   // 64 bf16 already packed
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const uint32_t w[4] = {rowbits[c].x, rowbits[c].y, rowbits[c].z, rowbits[c].w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            *reinterpret_cast<uint16_t*>(img + (8 * c + 2 * e) * TP + col * 2) = (uint16_t)(w[e] & 0xffffu);
-            *reinterpret_cast<uint16_t*>(img + (8 * c + 2 * e + 1) * TP + col * 2) = (uint16_t)(w[e] >> 16);
-        }
-    }
-}
-
-
-typedef short tr4s_t __attribute__((ext_vector_type(4)));
-// transposed fragment out of a row-major swizzled bf16 image (ds_read_b64_tr_b16): lane (fr, gq) gets column 16 dt + fr of rows row0 .. row0 + 3 and row0 + 16 .. + 19
-__device__ __forceinline__ uint4 rows_frag_tr(const char* img, int row0, int dt, int fr) {
-    const int c = 16 * dt + 4 * (fr & 3);
-    const int ra = row0 + (fr >> 2), rb = ra + 16;
-    const int oa = ra * 128 + (((c >> 3) ^ (ra & 7)) << 4) + (c & 7) * 2, ob = rb * 128 + (((c >> 3) ^ (rb & 7)) << 4) + (c & 7) * 2;
-    const tr4s_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tr4s_t*)(img + oa));
-    const tr4s_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tr4s_t*)(img + ob));
-    const uint2 l = __builtin_bit_cast(uint2, lo), hh = __builtin_bit_cast(uint2, hi);
-    return make_uint4(l.x, l.y, hh.x, hh.y);
-}
 
 // ===================================================================================================================
 // RVSA forward, 4 waves per (image, window, head): the bilinear gather is split over 256 threads (key x 16-channel quarter)
@@ -183,7 +42,7 @@ __global__ __launch_bounds__(256, 4) void rvsa_fwd4_mfma_kernel(const bf16_t* __
             // wave execute in order, so no barrier is involved (attn_rvsa_bwd4.hip does the same and keeps the records for its coordinate-gradient phase)
             const int l16 = lane & 15;
             const int key = (wave + 4 * (l16 >> 3)) * 8 + (l16 & 7), kc = key < 48 ? key : 48;
-            const Sample sm = make_sample(g, samp + (int64_t)bw * 5 * H, h, wi, wj, kc / 7, kc % 7);
+            const Sample sm = make_sample<true>(g, samp + (int64_t)bw * 5 * H, h, wi, wj, kc / 7, kc % 7);
             float wv[4];
             int tk[4];
 #pragma unroll
@@ -302,19 +161,6 @@ __global__ __launch_bounds__(256, 4) void rvsa_fwd4_mfma_kernel(const bf16_t* __
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) store4(op + 16 * dt, make_float4(oa[dt][0] * inv, oa[dt][1] * inv, oa[dt][2] * inv, oa[dt][3] * inv));
     }
-}
-
-RvsaGeom make_geom(int64_t Hp, int64_t Wp, int64_t heads) {
-    RvsaGeom g;
-    const int pad_h = (int)((7 - Hp % 7) % 7), pad_w = (int)((7 - Wp % 7) % 7);
-    g.Hp = (int)Hp; g.Wp = (int)Wp;
-    g.pad_t = pad_h / 2; g.pad_l = pad_w / 2;
-    g.He = (int)Hp + pad_h; g.We = (int)Wp + pad_w;
-    g.nh = g.He / 7; g.nw = g.We / 7;
-    g.heads = (int)heads;
-    g.inv_div_x = 1.0f / (float)(Hp / 7);
-    g.inv_div_y = 1.0f / (float)(Wp / 7);
-    return g;
 }
 
 }  // namespace

@@ -995,6 +995,82 @@ torch.save({"dqkv": dqkv.float().cpu(), "dsamp": dsamp.cpu()}, sys.argv[1])
     assert rel_err(outs["dense"]["dqkv"], outs["gemm"]["dqkv"]) < 1e-2 and rel_err(outs["dense"]["dsamp"], outs["gemm"]["dsamp"]) < 1e-3
 
 
+# grid -> {output: (relative difference between the two kernels measured on the MI355X, bound = 4 x that)}.
+#   drel (drel_h | drel_w): rvsa_bwd5_mfma_kernel sums the queries of a table row in the slot order of its transpose reads, rvsa_bwd4_mfma_kernel in query
+#         order; on top of that the per-workgroup partials are summed with f32 atomics (mtp_reduce_rows_f32 splits the rows over workgroups), whose order
+#         changes from run to run -- 8 x 9, where one kernel runs twice (see the test), shows that part alone.
+#   dsamp: the coordinate gradients are dot products of the (bf16) dK_sel | dV_sel rows with the neighbour rows: the same products, summed by v_dot2_f32_bf16
+#         in two chains in rvsa_bwd5_mfma_kernel and by f32 multiply-adds in one chain in rvsa_bwd4_mfma_kernel.  (The kernel's header comment used to call
+#         dsamp bit-identical; it never was.)
+# drel is the largest of three runs (14 x 14: 1.70e-7, 1.70e-7, 1.13e-7); dsamp repeats to the digit.
+RVSA_BWD_KERNELS_REL = {(14, 14): dict(drel=(1.71e-7, 6.84e-7), dsamp=(1.02e-7, 4.08e-7)), (8, 9): dict(drel=(1.52e-7, 6.08e-7), dsamp=(0.0, 0.0)),
+                        (12, 10): dict(drel=(1.81e-7, 7.24e-7), dsamp=(1.19e-7, 4.76e-7))}
+
+
+def test_rvsa_backward_kernels_agree_bit_for_bit_in_subprocesses(ops, tmp_path):
+    """rvsa_bwd5_mfma_kernel (the default) against rvsa_bwd4_mfma_kernel (MTP_RVSA_BWD=4 -- read once per process, hence the subprocesses) on the same
+    inputs: both draw their sampling geometry and lane helpers from attn_rvsa_common.h and issue the same MFMAs on the same operand values, so dqkv and the
+    bias-table gradient (one reduction workgroup at these sizes: no atomics) are equal bit for bit; the rel-pos table gradients and dsamp are sums of the
+    same terms in another order or precision and are held to RVSA_BWD_KERNELS_REL.
+    14 x 14: whole windows.  12 x 10: padded on both axes by different amounts (pad_t = 1, pad_l = 2).  Both take the dense-product scatter: no atomics.
+    8 x 9 (pad_t = 3, pad_l = 2) is mostly padding (N < 24.5 nW) and takes the in-kernel atomic scatter, where MTP_RVSA_BWD selects nothing: one kernel runs
+    twice, dsamp agrees to the bit, and the dk | dv columns differ only in the order of f32 atomics, i.e. by at most one bf16 unit in the last place (2^-7 of
+    the element) once the sums are rounded."""
+    import subprocess
+    import sys
+    grids = sorted(RVSA_BWD_KERNELS_REL)
+    code = """
+import sys, torch
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+from mtp_amd import ops
+B, heads, hd = 2, 2, 64
+out = {}
+for Hp, Wp in %r:
+    C, T = heads * hd, B * Hp * Wp
+    nh, nw = ops.rvsa_windows(Hp, Wp)
+    R = B * nh * nw
+    g = torch.Generator().manual_seed(5)
+    qkv = (0.5 * torch.randn(T, 3 * C, generator=g)).cuda().bfloat16()
+    samp = (0.3 * torch.randn(R, 5 * heads, generator=g)).cuda()
+    rh, rw, tab = (0.3 * torch.randn(13, hd, generator=g)).cuda(), (0.3 * torch.randn(13, hd, generator=g)).cuda(), (0.3 * torch.randn(169, heads, generator=g)).cuda()
+    do = torch.randn(T, C, generator=g).cuda().bfloat16()
+    o, lse = torch.empty(T, C, device="cuda", dtype=torch.bfloat16), torch.empty(R * heads * 49, device="cuda")
+    ops.rvsa_attn_fwd(qkv, samp, o, lse, rh, rw, tab, B, Hp, Wp, heads, hd ** -0.5)
+    dqkv, dsamp = torch.empty(T, 3 * C, device="cuda", dtype=torch.bfloat16), torch.empty(R, 5 * heads, device="cuda")
+    d1, d2, d3 = torch.zeros(13, hd, device="cuda"), torch.zeros(13, hd, device="cuda"), torch.zeros(169, heads, device="cuda")
+    ops.rvsa_attn_bwd(qkv, samp, o, do, lse, dqkv, dsamp, rh, rw, tab, d1, d2, d3, B, Hp, Wp, heads, hd ** -0.5)
+    torch.cuda.synchronize()
+    out[(Hp, Wp)] = {"dqkv": dqkv.cpu(), "dsamp": dsamp.cpu(), "drel_h": d1.cpu(), "drel_w": d2.cpu(), "dtab": d3.cpu()}
+torch.save(out, sys.argv[1])
+""" % (ROOT, os.path.join(ROOT, "tests"), grids)
+    outs = {}
+    for kernel in ("5", "4"):
+        f = str(tmp_path / ("bwd" + kernel + ".pt"))
+        env = {k: v for k, v in os.environ.items() if k != "MTP_RVSA_BWD"}
+        if kernel == "4":
+            env["MTP_RVSA_BWD"] = "4"
+        r = subprocess.run([sys.executable, "-c", code, f], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        outs[kernel] = torch.load(f)
+    C = 2 * 64
+    fig = {}
+    for grid in grids:      # every figure first, then the assertions
+        a, b = outs["5"][grid], outs["4"][grid]
+        fig[grid] = dict(drel=max(rel_err(a["drel_h"], b["drel_h"]), rel_err(a["drel_w"], b["drel_w"])), dsamp=rel_err(a["dsamp"], b["dsamp"]),
+                         dkv=rel_err(a["dqkv"][:, C:].float(), b["dqkv"][:, C:].float()),
+                         dq_bits=torch.equal(a["dqkv"][:, :C], b["dqkv"][:, :C]), dkv_bits=torch.equal(a["dqkv"][:, C:], b["dqkv"][:, C:]),
+                         dsamp_bits=torch.equal(a["dsamp"], b["dsamp"]), dtab_bits=torch.equal(a["dtab"], b["dtab"]),
+                         finite=all(bool(torch.isfinite(t.float()).all()) for t in list(a.values()) + list(b.values())))
+        print("rvsa bwd5 vs bwd4 %s: %s" % (grid, fig[grid]))
+    for grid in grids:
+        f, bound = fig[grid], RVSA_BWD_KERNELS_REL[grid]
+        dense = ops.rvsa_attn_kernel(torch.bfloat16, grid[0], grid[1], 2, backward=True) == ops.RVSA_BWD["mfma_dense"]
+        assert dense == (grid != (8, 9)), grid
+        assert f["finite"] and f["dq_bits"] and f["dtab_bits"], (grid, f)
+        assert f["dkv_bits"] if dense else f["dkv"] <= 2.0 ** -7 and f["dsamp_bits"], (grid, f)
+        assert f["drel"] <= bound["drel"][1] and f["dsamp"] <= bound["dsamp"][1], (grid, f)
+
+
 # ---- the attention kernels at the launch geometry of the headline benchmark: 64 images x 16 heads x 64 dims (ViT-L, B = 64)
 @pytest.mark.parametrize("dtype", DT)
 def test_full_attention_at_vit_l_b64_geometry(ops, dtype):
