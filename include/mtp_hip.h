@@ -288,6 +288,22 @@ int mtp_dwconv3x3_fwd(const void* x, const float* w, const float* bias, void* y,
 int mtp_dwconv3x3_bwd_dx(const void* dy, int dtype, const float* w, float* dx, int accumulate, int64_t N, int64_t H, int64_t W, int64_t C, mtp_stream_t stream);
 int64_t mtp_dwconv3x3_bwd_dw_partial_rows(int64_t N, int64_t H, int64_t W);
 int mtp_dwconv3x3_bwd_dw(const void* dy, const void* x, int dtype, float* part, int64_t N, int64_t H, int64_t W, int64_t C, mtp_stream_t stream);
+/* Which kernel mtp_im2col3x3 / mtp_col2im3x3 / mtp_dwconv3x3_fwd / _bwd_dx / _bwd_dw run -- the operators of this section that have more than one: the
+ * value of the very decision the entry points launch by (one function serves both), no launch, no device needed.  `op` selects the operator, the other
+ * arguments are that operator's own, under common names: src = x / dcols / dy (src_dtype its dtype), dst = cols / dx / y / part (dst_dtype: im2col's
+ * cols_dtype, ignored otherwise), (sN, sH, sW, sC), stride and Kp for the two 3x3 gathers only, w / bias for the depth-wise forward (bias may be NULL)
+ * and data gradient (w), C = Cin for the gathers.  Returns the error the entry point would return for these arguments (MTP_ERR_ARG), or
+ * MTP_CONV_KERNEL_NONE where it would return MTP_ERR_UNSUPPORTED. */
+typedef enum { MTP_CONV_OP_IM2COL3X3 = 0, MTP_CONV_OP_COL2IM3X3 = 1, MTP_CONV_OP_DWCONV3X3_FWD = 2, MTP_CONV_OP_DWCONV3X3_BWD_DX = 3, MTP_CONV_OP_DWCONV3X3_BWD_DW = 4 } mtp_conv_op;
+typedef enum {
+    MTP_CONV_KERNEL_NONE = 0,
+    MTP_CONV_KERNEL_ELEMENT = 1,  /* one element (3x3 gathers) resp. one pixel x 4 channels (depth-wise) per lane: any dtype, stride and alignment */
+    MTP_CONV_KERNEL_V8 = 2,       /* 3x3 gathers, 8 channels per lane: bf16, channels-last, Cin % 8 == 0, Kp % 8 == 0, 16-byte aligned */
+    MTP_CONV_KERNEL_P8 = 3,       /* depth-wise forward / data gradient, 8 pixels of a row per lane: bf16, W % 8 == 0, 16-byte aligned weights */
+    MTP_CONV_KERNEL_PX4 = 4       /* depth-wise weight gradient, 4 pixels of a row per step: bf16, W % 4 == 0 */
+} mtp_conv_kernel_family;
+int mtp_conv_kernel(int op, const void* src, int src_dtype, int64_t sN, int64_t sH, int64_t sW, int64_t sC, const void* dst, int dst_dtype,
+                    const float* w, const float* bias, int64_t N, int64_t H, int64_t W, int64_t C, int64_t stride, int64_t Kp);
 /* The same for any odd k (InternImage-H/G's dw_kernel_size, ops_dcnv3/modules/dcnv3.py:124, 146-151): plain per-(pixel, 4 channels) kernels; w (C, 1, k, k) f32.
  * mtp_dwconv_bwd_dw ACCUMULATES into dw / db with f32 atomics (clear them first); db may be NULL.  (k = 3: the mtp_dwconv3x3_* entries above are the fast path.) */
 int mtp_dwconv_fwd(const void* x, const float* w, const float* bias, void* y, int dtype, int64_t N, int64_t H, int64_t W, int64_t C, int k, mtp_stream_t stream);
@@ -449,6 +465,27 @@ int mtp_dcnv3_bwd(const void* input, const void* offset, const void* mask, const
  * the backward (every InternImage level); MTP_ERR_UNSUPPORTED otherwise, with nothing launched. */
 int mtp_dcnv3_bwd_act(const void* input, const void* offset, const void* mask, const void* grad_output, int dtype, float* grad_input, float* grad_offset,
                       float* grad_mask, void* grad_offset_act, int64_t act_ld, const mtp_dcnv3_geom* geom, mtp_stream_t stream);
+
+/* Which kernels mtp_dcnv3_fwd (backward == 0: input, offset, mask, out = output; the three gradient pointers are ignored) resp. mtp_dcnv3_bwd
+ * (out = grad_output) run for these pointers, this dtype and geometry: the value of the very decision the entry points launch by (one function serves
+ * both, with every check that precedes it), no launch, no device needed.  Returns MTP_ERR_ARG where the entry point would, MTP_DCNV3_KERNEL_NONE where it
+ * would return MTP_ERR_UNSUPPORTED (a map beyond the 32-bit limits), else the family.  It speaks for mtp_dcnv3_fwd and mtp_dcnv3_bwd only: mtp_dcnv3_bwd_act
+ * launches the same backward family where that is a gather form and returns MTP_ERR_UNSUPPORTED where this query says BWD_SCATTER_*. */
+typedef enum {
+    MTP_DCNV3_KERNEL_NONE = 0,
+    MTP_DCNV3_FWD9 = 1,                /* the unrolled 3 x 3 forward, 8 channels per lane */
+    MTP_DCNV3_FWD_VEC8 = 2,            /* the generic forward, 8 channels per lane (group_channels % 8 == 0, 16-byte aligned maps) */
+    MTP_DCNV3_FWD_SCALAR = 3,          /* the generic forward, one channel per lane */
+    MTP_DCNV3_F64 = 4,                 /* the double kernels, forward and backward */
+    MTP_DCNV3_BWD_WINDOW_R2 = 5,       /* gather form, window reach 2 */
+    MTP_DCNV3_BWD_WINDOW_R3 = 6,       /* gather form, window reach 3 */
+    MTP_DCNV3_BWD_3X3_OS1 = 7,         /* gather form, 3 x 3 form for offset_scale 1 (variant bit 2) */
+    MTP_DCNV3_BWD_3X3_OS2 = 8,         /* ... for offset_scale 2 */
+    MTP_DCNV3_BWD_SCATTER_SHFL = 9,    /* per-corner atomic scatter, channel sums by butterflies (group_channels a power of two <= 64) */
+    MTP_DCNV3_BWD_SCATTER_ATOMIC = 10  /* ... by f32 atomics */
+} mtp_dcnv3_kernel_family;
+int mtp_dcnv3_kernel(const void* input, const void* offset, const void* mask, const void* out, const float* grad_input, const float* grad_offset,
+                     const float* grad_mask, int dtype, const mtp_dcnv3_geom* geom, int backward);
 
 const char* mtp_version(void);
 

@@ -26,6 +26,12 @@ GEMM_STORE_SHIFT, GEMM_STORE_NT, GEMM_STORE_SC1, GEMM_STORE_PLAIN, GEMM_STORE_MA
 # enum mtp_gemm_nt_family (GemmNtPlan.family)
 GEMM_NT_FAMILY_SB, GEMM_NT_FAMILY_SB8, GEMM_NT_FAMILY_REG, GEMM_NT_FAMILY_P8, GEMM_NT_FAMILY_STRIP = 0, 1, 2, 3, 4
 
+# enum mtp_conv_op / mtp_conv_kernel_family (mtp_conv_kernel) and mtp_dcnv3_kernel_family (mtp_dcnv3_kernel)
+CONV_OP_IM2COL3X3, CONV_OP_COL2IM3X3, CONV_OP_DWCONV3X3_FWD, CONV_OP_DWCONV3X3_BWD_DX, CONV_OP_DWCONV3X3_BWD_DW = 0, 1, 2, 3, 4
+CONV_KERNEL_NONE, CONV_KERNEL_ELEMENT, CONV_KERNEL_V8, CONV_KERNEL_P8, CONV_KERNEL_PX4 = 0, 1, 2, 3, 4
+DCNV3_KERNEL_NONE, DCNV3_FWD9, DCNV3_FWD_VEC8, DCNV3_FWD_SCALAR, DCNV3_F64 = 0, 1, 2, 3, 4
+DCNV3_BWD_WINDOW_R2, DCNV3_BWD_WINDOW_R3, DCNV3_BWD_3X3_OS1, DCNV3_BWD_3X3_OS2, DCNV3_BWD_SCATTER_SHFL, DCNV3_BWD_SCATTER_ATOMIC = 5, 6, 7, 8, 9, 10
+
 p, i64, i32, f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
 
 
@@ -68,6 +74,8 @@ SIGNATURES = {
     "mtp_dcnv3_fwd": (i32, [p, p, p, p, i32, C.POINTER(Dcnv3Geom), p]),
     "mtp_dcnv3_bwd": (i32, [p, p, p, p, i32, p, p, p, C.POINTER(Dcnv3Geom), p]),
     "mtp_dcnv3_bwd_act": (i32, [p, p, p, p, i32, p, p, p, p, i64, C.POINTER(Dcnv3Geom), p]),
+    "mtp_dcnv3_kernel": (i32, [p, p, p, p, p, p, p, i32, C.POINTER(Dcnv3Geom), i32]),
+    "mtp_conv_kernel": (i32, [i32, p, i32, i64, i64, i64, i64, p, i32, p, p, i64, i64, i64, i64, i64, i64]),
     "mtp_gemm_nt": (i32, [C.POINTER(GemmArgs), p]),
     "mtp_gemm_nt_plan": (i32, [C.POINTER(GemmArgs), i32, C.POINTER(GemmNtPlan)]),
     "mtp_gemm_nt_tile": (i32, [C.POINTER(GemmArgs)]),

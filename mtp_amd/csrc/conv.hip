@@ -614,16 +614,61 @@ __global__ __launch_bounds__(256) void cfs_kernel(const T* __restrict__ a0, cons
     }
 }
 
+// ---- the dispatch of the operators that have more than one kernel: the argument checks and the choice in ONE function per operator.  The entry points
+// below launch what these name and mtp_conv_kernel reports the same value (the edge tests assert it per case): < 0 = the error the entry point
+// returns, MTP_CONV_KERNEL_NONE = it returns MTP_ERR_UNSUPPORTED.
+int im2col3x3_family(const void* x, int x_dtype, int64_t sN, int64_t sH, int64_t sW, int64_t sC, const void* cols, int cols_dtype,
+                     int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t stride, int64_t Kp) {
+    if (!x || !cols || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || stride < 1 || Kp < 9 * Cin) return MTP_ERR_ARG;
+    const int64_t Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;      // (H + 2 - 3) / s + 1
+    if (N * Ho * Wo * Kp / 256 > 0x7fffffff) return MTP_ERR_ARG;
+    if (x_dtype == MTP_BF16 && cols_dtype == MTP_BF16 && sC == 1 && !(Cin & 7) && !(Kp & 7) && !((sN | sH | sW) & 7) && !(((uintptr_t)x | (uintptr_t)cols) & 15))
+        return MTP_CONV_KERNEL_V8;
+    const bool ok = (x_dtype == MTP_F32 && (cols_dtype == MTP_F32 || cols_dtype == MTP_BF16)) || (x_dtype == MTP_BF16 && cols_dtype == MTP_BF16);
+    return ok ? MTP_CONV_KERNEL_ELEMENT : MTP_CONV_KERNEL_NONE;
+}
+int col2im3x3_family(const void* dcols, int cols_dtype, const float* dx, int64_t sN, int64_t sH, int64_t sW, int64_t sC,
+                     int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t stride, int64_t Kp) {
+    if (!dcols || !dx || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || stride < 1 || Kp < 9 * Cin) return MTP_ERR_ARG;
+    if (cols_dtype == MTP_BF16 && sC == 1 && !(Cin & 7) && !(Kp & 7) && !((sN | sH | sW) & 7) && !(((uintptr_t)dcols | (uintptr_t)dx) & 15)) return MTP_CONV_KERNEL_V8;
+    return (cols_dtype == MTP_BF16 || cols_dtype == MTP_F32) ? MTP_CONV_KERNEL_ELEMENT : MTP_CONV_KERNEL_NONE;
+}
+// forward (bias may be NULL) and data gradient (bias = NULL): x resp. dy, w, y resp. dx
+int dwconv3x3_family(const void* x, const float* w, const float* bias, const void* y, int dtype, int64_t N, int64_t H, int64_t W, int64_t C) {
+    if (!x || !w || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 4)) return MTP_ERR_ARG;
+    if (N * H * W * (C / 4) >= ((int64_t)1 << 31)) return MTP_CONV_KERNEL_NONE;      // 32-bit index arithmetic in the kernels
+    if (dtype == MTP_BF16 && !(W & 7) && !(((uintptr_t)w | (uintptr_t)(bias ? bias : w)) & 15)) return MTP_CONV_KERNEL_P8;
+    return (dtype == MTP_BF16 || dtype == MTP_F32) ? MTP_CONV_KERNEL_ELEMENT : MTP_CONV_KERNEL_NONE;
+}
+int dwconv3x3_dw_family(const void* dy, const void* x, int dtype, const float* part, int64_t N, int64_t H, int64_t W, int64_t C) {
+    if (!dy || !x || !part || N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 4)) return MTP_ERR_ARG;
+    if (dtype == MTP_BF16 && !(W & 3)) return MTP_CONV_KERNEL_PX4;
+    return (dtype == MTP_BF16 || dtype == MTP_F32) ? MTP_CONV_KERNEL_ELEMENT : MTP_CONV_KERNEL_NONE;
+}
+
 }  // namespace
+
+extern "C" int mtp_conv_kernel(int op, const void* src, int src_dtype, int64_t sN, int64_t sH, int64_t sW, int64_t sC, const void* dst, int dst_dtype,
+                               const float* w, const float* bias, int64_t N, int64_t H, int64_t W, int64_t C, int64_t stride, int64_t Kp) {
+    switch (op) {
+        case MTP_CONV_OP_IM2COL3X3: return im2col3x3_family(src, src_dtype, sN, sH, sW, sC, dst, dst_dtype, N, H, W, C, stride, Kp);
+        case MTP_CONV_OP_COL2IM3X3: return col2im3x3_family(src, src_dtype, (const float*)dst, sN, sH, sW, sC, N, H, W, C, stride, Kp);
+        case MTP_CONV_OP_DWCONV3X3_FWD: return dwconv3x3_family(src, w, bias, dst, src_dtype, N, H, W, C);
+        case MTP_CONV_OP_DWCONV3X3_BWD_DX: return dwconv3x3_family(src, w, nullptr, dst, src_dtype, N, H, W, C);
+        case MTP_CONV_OP_DWCONV3X3_BWD_DW: return dwconv3x3_dw_family(src, src, src_dtype, (const float*)dst, N, H, W, C);
+        default: return MTP_ERR_ARG;
+    }
+}
 
 extern "C" int mtp_im2col3x3(const void* x, int x_dtype, int64_t sN, int64_t sH, int64_t sW, int64_t sC, void* cols, int cols_dtype,
                              int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t stride, int64_t Kp, mtp_stream_t stream) {
-    if (!x || !cols || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || stride < 1 || Kp < 9 * Cin) return MTP_ERR_ARG;
+    const int fam = im2col3x3_family(x, x_dtype, sN, sH, sW, sC, cols, cols_dtype, N, H, W, Cin, stride, Kp);
+    if (fam < 0) return fam;
+    if (fam == MTP_CONV_KERNEL_NONE) return MTP_ERR_UNSUPPORTED;
     const int Ho = (int)((H - 1) / stride + 1), Wo = (int)((W - 1) / stride + 1);      // (H + 2 - 3) / s + 1
     const int64_t total = N * Ho * Wo * Kp;
-    if (total / 256 > 0x7fffffff) return MTP_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    if (x_dtype == MTP_BF16 && cols_dtype == MTP_BF16 && sC == 1 && !(Cin & 7) && !(Kp & 7) && !((sN | sH | sW) & 7) && !(((uintptr_t)x | (uintptr_t)cols) & 15)) {
+    if (fam == MTP_CONV_KERNEL_V8) {
         const int64_t total8 = total / 8;
         hipLaunchKernelGGL(im2col3x3_v8_kernel, dim3(blocks_for(total8)), dim3(256), 0, s, (const bf16_t*)x, sN, sH, sW, (bf16_t*)cols, (int)H, (int)W, (int)Cin, Ho, Wo, (int)stride, (int)Kp, total8);
         return mtp_launch_status();
@@ -632,19 +677,20 @@ extern "C" int mtp_im2col3x3(const void* x, int x_dtype, int64_t sN, int64_t sH,
 #define MTP_LAUNCH_I2C(TX, TC) hipLaunchKernelGGL((im2col3x3_kernel<TX, TC>), grid, block, 0, s, (const TX*)x, sN, sH, sW, sC, (TC*)cols, (int)H, (int)W, (int)Cin, Ho, Wo, (int)stride, (int)Kp, total)
     if (x_dtype == MTP_F32 && cols_dtype == MTP_F32) MTP_LAUNCH_I2C(float, float);
     else if (x_dtype == MTP_F32 && cols_dtype == MTP_BF16) MTP_LAUNCH_I2C(float, bf16_t);
-    else if (x_dtype == MTP_BF16 && cols_dtype == MTP_BF16) MTP_LAUNCH_I2C(bf16_t, bf16_t);
-    else return MTP_ERR_UNSUPPORTED;
+    else MTP_LAUNCH_I2C(bf16_t, bf16_t);
 #undef MTP_LAUNCH_I2C
     return mtp_launch_status();
 }
 
 extern "C" int mtp_col2im3x3(const void* dcols, int cols_dtype, float* dx, int64_t sN, int64_t sH, int64_t sW, int64_t sC,
                              int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t stride, int64_t Kp, int accumulate, mtp_stream_t stream) {
-    if (!dcols || !dx || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || stride < 1 || Kp < 9 * Cin) return MTP_ERR_ARG;
+    const int fam = col2im3x3_family(dcols, cols_dtype, dx, sN, sH, sW, sC, N, H, W, Cin, stride, Kp);
+    if (fam < 0) return fam;
+    if (fam == MTP_CONV_KERNEL_NONE) return MTP_ERR_UNSUPPORTED;
     const int Ho = (int)((H - 1) / stride + 1), Wo = (int)((W - 1) / stride + 1);
     const int64_t total = N * H * W * Cin;
     hipStream_t s = (hipStream_t)stream;
-    if (cols_dtype == MTP_BF16 && sC == 1 && !(Cin & 7) && !(Kp & 7) && !((sN | sH | sW) & 7) && !(((uintptr_t)dcols | (uintptr_t)dx) & 15)) {
+    if (fam == MTP_CONV_KERNEL_V8) {
         const int64_t total8 = total / 8;
         hipLaunchKernelGGL(col2im3x3_v8_kernel, dim3(blocks_for(total8)), dim3(256), 0, s, (const bf16_t*)dcols, dx, sN, sH, sW, (int)H, (int)W, (int)Cin, Ho, Wo, (int)stride, (int)Kp, accumulate, total8);
         return mtp_launch_status();
@@ -652,9 +698,8 @@ extern "C" int mtp_col2im3x3(const void* dcols, int cols_dtype, float* dx, int64
     const dim3 grid(blocks_for(total)), block(256);
     if (cols_dtype == MTP_BF16)
         hipLaunchKernelGGL((col2im3x3_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)dcols, dx, sN, sH, sW, sC, (int)H, (int)W, (int)Cin, Ho, Wo, (int)stride, (int)Kp, accumulate, total);
-    else if (cols_dtype == MTP_F32)
+    else
         hipLaunchKernelGGL((col2im3x3_kernel<float>), grid, block, 0, s, (const float*)dcols, dx, sN, sH, sW, sC, (int)H, (int)W, (int)Cin, Ho, Wo, (int)stride, (int)Kp, accumulate, total);
-    else return MTP_ERR_UNSUPPORTED;
     return mtp_launch_status();
 }
 
@@ -685,34 +730,34 @@ extern "C" int mtp_pack_rows_padded(const float* w, void* wp, void* wpt, int dty
 }
 
 extern "C" int mtp_dwconv3x3_fwd(const void* x, const float* w, const float* bias, void* y, int dtype, int64_t N, int64_t H, int64_t W, int64_t C, mtp_stream_t stream) {
-    if (!x || !w || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 4)) return MTP_ERR_ARG;
+    const int fam = dwconv3x3_family(x, w, bias, y, dtype, N, H, W, C);
+    if (fam < 0) return fam;
+    if (fam == MTP_CONV_KERNEL_NONE) return MTP_ERR_UNSUPPORTED;
     const int64_t total = N * H * W * (C / 4);
-    if (total >= ((int64_t)1 << 31)) return MTP_ERR_UNSUPPORTED;      // 32-bit index arithmetic in the kernel
     const dim3 grid(blocks_for(total)), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == MTP_BF16 && !(W & 7) && !(((uintptr_t)w | (uintptr_t)(bias ? bias : w)) & 15)) {
+    if (fam == MTP_CONV_KERNEL_P8) {
         hipLaunchKernelGGL((dwconv3x3_p8_kernel<bf16_t, false>), dim3(blocks_for(total / 8)), block, 0, s, (const bf16_t*)x, w, bias, (bf16_t*)y, (int)H, (int)W, (int)C, 0, total / 8);
         return mtp_launch_status();
     }
     if (dtype == MTP_BF16) hipLaunchKernelGGL((dwconv3x3_kernel<bf16_t, bf16_t, false>), grid, block, 0, s, (const bf16_t*)x, w, bias, (bf16_t*)y, (int)H, (int)W, (int)C, 0, total);
-    else if (dtype == MTP_F32) hipLaunchKernelGGL((dwconv3x3_kernel<float, float, false>), grid, block, 0, s, (const float*)x, w, bias, (float*)y, (int)H, (int)W, (int)C, 0, total);
-    else return MTP_ERR_UNSUPPORTED;
+    else hipLaunchKernelGGL((dwconv3x3_kernel<float, float, false>), grid, block, 0, s, (const float*)x, w, bias, (float*)y, (int)H, (int)W, (int)C, 0, total);
     return mtp_launch_status();
 }
 
 extern "C" int mtp_dwconv3x3_bwd_dx(const void* dy, int dtype, const float* w, float* dx, int accumulate, int64_t N, int64_t H, int64_t W, int64_t C, mtp_stream_t stream) {
-    if (!dy || !w || !dx || N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 4)) return MTP_ERR_ARG;
+    const int fam = dwconv3x3_family(dy, w, nullptr, dx, dtype, N, H, W, C);
+    if (fam < 0) return fam;
+    if (fam == MTP_CONV_KERNEL_NONE) return MTP_ERR_UNSUPPORTED;
     const int64_t total = N * H * W * (C / 4);
-    if (total >= ((int64_t)1 << 31)) return MTP_ERR_UNSUPPORTED;      // 32-bit index arithmetic in the kernel
     const dim3 grid(blocks_for(total)), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == MTP_BF16 && !(W & 7) && !((uintptr_t)w & 15)) {
+    if (fam == MTP_CONV_KERNEL_P8) {
         hipLaunchKernelGGL((dwconv3x3_p8_kernel<float, true>), dim3(blocks_for(total / 8)), block, 0, s, (const bf16_t*)dy, w, (const float*)nullptr, dx, (int)H, (int)W, (int)C, accumulate, total / 8);
         return mtp_launch_status();
     }
     if (dtype == MTP_BF16) hipLaunchKernelGGL((dwconv3x3_kernel<bf16_t, float, true>), grid, block, 0, s, (const bf16_t*)dy, w, (const float*)nullptr, dx, (int)H, (int)W, (int)C, accumulate, total);
-    else if (dtype == MTP_F32) hipLaunchKernelGGL((dwconv3x3_kernel<float, float, true>), grid, block, 0, s, (const float*)dy, w, (const float*)nullptr, dx, (int)H, (int)W, (int)C, accumulate, total);
-    else return MTP_ERR_UNSUPPORTED;
+    else hipLaunchKernelGGL((dwconv3x3_kernel<float, float, true>), grid, block, 0, s, (const float*)dy, w, (const float*)nullptr, dx, (int)H, (int)W, (int)C, accumulate, total);
     return mtp_launch_status();
 }
 
@@ -724,19 +769,20 @@ extern "C" int64_t mtp_dwconv3x3_bwd_dw_partial_rows(int64_t N, int64_t H, int64
 
 /* part: (mtp_dwconv3x3_bwd_dw_partial_rows, 10 C) f32 = per-block partials of [dweight (C, 9) | dbias (C)] */
 extern "C" int mtp_dwconv3x3_bwd_dw(const void* dy, const void* x, int dtype, float* part, int64_t N, int64_t H, int64_t W, int64_t C, mtp_stream_t stream) {
-    if (!dy || !x || !part || N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 4)) return MTP_ERR_ARG;
+    const int fam = dwconv3x3_dw_family(dy, x, dtype, part, N, H, W, C);
+    if (fam < 0) return fam;
+    if (fam == MTP_CONV_KERNEL_NONE) return MTP_ERR_UNSUPPORTED;
     const int64_t pixels = N * H * W, nb = mtp_dwconv3x3_bwd_dw_partial_rows(N, H, W);
     const int64_t ppb = (pixels + nb - 1) / nb;
     const dim3 grid((unsigned)((C / 4 + 63) / 64), (unsigned)nb), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == MTP_BF16 && !(W & 3)) {      // blocks of whole 4-pixel groups (the last blocks may be empty: they write zero partials)
+    if (fam == MTP_CONV_KERNEL_PX4) {      // blocks of whole 4-pixel groups (the last blocks may be empty: they write zero partials)
         const int64_t ppb4 = (ppb + 3) / 4 * 4;
         hipLaunchKernelGGL(dwconv3x3_dw_px_kernel<4>, grid, block, 0, s, (const bf16_t*)dy, (const bf16_t*)x, part, (int)H, (int)W, (int)C, pixels, ppb4);
         return mtp_launch_status();
     }
     if (dtype == MTP_BF16) hipLaunchKernelGGL((dwconv3x3_dw_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)dy, (const bf16_t*)x, part, (int)H, (int)W, (int)C, pixels, ppb);
-    else if (dtype == MTP_F32) hipLaunchKernelGGL((dwconv3x3_dw_kernel<float>), grid, block, 0, s, (const float*)dy, (const float*)x, part, (int)H, (int)W, (int)C, pixels, ppb);
-    else return MTP_ERR_UNSUPPORTED;
+    else hipLaunchKernelGGL((dwconv3x3_dw_kernel<float>), grid, block, 0, s, (const float*)dy, (const float*)x, part, (int)H, (int)W, (int)C, pixels, ppb);
     return mtp_launch_status();
 }
 

@@ -805,14 +805,44 @@ int make_geom(const mtp_dcnv3_geom* a, DcnGeom& g) {
 }
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-template <typename T>
-int launch_fwd(const void* input, const void* offset, const void* mask, void* output, const DcnGeom& g, hipStream_t s) {
-    const int64_t items = (int64_t)g.N * g.Ho * g.Wo * g.G;
+// ---- the dispatch: which kernels take (pointers, geometry).  launch_fwd / launch_bwd launch what these name and mtp_dcnv3_kernel reports the same
+// value (the edge tests assert it per case).
+int fwd_family(const void* input, const void* offset, const void* output, const DcnGeom& g) {
     if (g.GC % 8 == 0 && aligned16(input) && aligned16(output) && g.kh == 3 && g.kw == 3 && !g.remove_center && !g.fwd_generic &&
-        (reinterpret_cast<uintptr_t>(offset) & 7u) == 0) {
+        (reinterpret_cast<uintptr_t>(offset) & 7u) == 0)
+        return MTP_DCNV3_FWD9;
+    if (g.GC % 8 == 0 && aligned16(input) && aligned16(output)) return MTP_DCNV3_FWD_VEC8;
+    return MTP_DCNV3_FWD_SCALAR;
+}
+int bwd_family(const void* input, const void* grad_output, const float* grad_input, const float* grad_offset, const DcnGeom& g) {
+    // the gather form (no scatter): stride 1, "same" padding, 16-channel groups, <= 9 points, reach R <= 3
+    const int halfw = (g.dw * (g.kw - 1)) >> 1, halfh = (g.dh * (g.kh - 1)) >> 1;
+    const int reach = (int)ceilf((float)(halfw > halfh ? halfw : halfh) * fabsf(g.os)) + 1;
+    if (!g.scatter_bwd && g.GC == 16 && g.P <= 9 && g.sh == 1 && g.sw == 1 && g.Ho == g.H && g.Wo == g.W && g.ph == halfh && g.pw == halfw && reach <= 3 &&
+        aligned16(input) && aligned16(grad_output) && aligned16(grad_input) && (reinterpret_cast<uintptr_t>(grad_offset) & 7u) == 0) {
+        const int tiles_x = (g.W + DT_TILE - 1) / DT_TILE, tiles_y = (g.H + DT_TILE - 1) / DT_TILE;
+        const int64_t blocks = (int64_t)g.N * tiles_y * tiles_x * g.G, items = (int64_t)g.N * g.Ho * g.Wo * g.G;
+        if (blocks < ((int64_t)1 << 31) && 2 * items < ((int64_t)1 << 32) - 256) {
+            // default: the window form.  The 3 x 3 form is 8 % faster for offsets below a pixel (a freshly initialised network: the offset head starts at
+            // zero) but its reach is one pixel around the nominal position -- with offsets of sigma = 0.5 ... 1.6 px (bench.py re-draws the heads like
+            // fixture f12) 13 ... 77 % of the samples leave it and go through the atomics: InternImage-XL step 72.7 vs 69.1 ms (same box).
+            if (g.kh == 3 && g.kw == 3 && g.dh == 1 && g.dw == 1 && g.form3x3_bwd) {
+                if (g.os == 1.0f) return MTP_DCNV3_BWD_3X3_OS1;
+                if (g.os == 2.0f) return MTP_DCNV3_BWD_3X3_OS2;
+            }
+            return reach <= 2 ? MTP_DCNV3_BWD_WINDOW_R2 : MTP_DCNV3_BWD_WINDOW_R3;
+        }
+    }
+    return (g.GC <= 64 && (g.GC & (g.GC - 1)) == 0) ? MTP_DCNV3_BWD_SCATTER_SHFL : MTP_DCNV3_BWD_SCATTER_ATOMIC;
+}
+
+template <typename T>
+int launch_fwd(const void* input, const void* offset, const void* mask, void* output, const DcnGeom& g, int fam, hipStream_t s) {
+    const int64_t items = (int64_t)g.N * g.Ho * g.Wo * g.G;
+    if (fam == MTP_DCNV3_FWD9) {
         const int64_t total = items * (g.GC / 8);
         hipLaunchKernelGGL((dcnv3_fwd9_kernel<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const T*)input, (const T*)offset, (const T*)mask, (T*)output, g, total);
-    } else if (g.GC % 8 == 0 && aligned16(input) && aligned16(output)) {
+    } else if (fam == MTP_DCNV3_FWD_VEC8) {
         const int64_t total = items * (g.GC / 8);
         hipLaunchKernelGGL((dcnv3_fwd_kernel<T, 8>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const T*)input, (const T*)offset, (const T*)mask, (T*)output, g, total);
     } else {
@@ -840,30 +870,21 @@ int launch_bwd_gather(const void* input, const void* offset, const void* mask, c
 
 template <typename T>
 int launch_bwd(const void* input, const void* offset, const void* mask, const void* grad_output, float* grad_input, float* grad_offset, float* grad_mask, const DcnGeom& g,
-               hipStream_t s) {
+               int fam, hipStream_t s) {
     const int64_t items = (int64_t)g.N * g.Ho * g.Wo * g.G, total = items * g.GC;
-    const bool shfl = g.GC <= 64 && (g.GC & (g.GC - 1)) == 0;
-    // the gather form (no scatter): stride 1, "same" padding, 16-channel groups, <= 9 points, reach R <= 3
-    const int halfw = (g.dw * (g.kw - 1)) >> 1, halfh = (g.dh * (g.kh - 1)) >> 1;
-    const int reach = (int)ceilf((float)(halfw > halfh ? halfw : halfh) * fabsf(g.os)) + 1;
-    if (!g.scatter_bwd && g.GC == 16 && g.P <= 9 && g.sh == 1 && g.sw == 1 && g.Ho == g.H && g.Wo == g.W && g.ph == halfh && g.pw == halfw && reach <= 3 &&
-        aligned16(input) && aligned16(grad_output) && aligned16(grad_input) && (reinterpret_cast<uintptr_t>(grad_offset) & 7u) == 0) {
+    const bool shfl = fam == MTP_DCNV3_BWD_SCATTER_SHFL;
+    if (fam != MTP_DCNV3_BWD_SCATTER_SHFL && fam != MTP_DCNV3_BWD_SCATTER_ATOMIC) {
         const int tiles_x = (g.W + DT_TILE - 1) / DT_TILE, tiles_y = (g.H + DT_TILE - 1) / DT_TILE;
         const int64_t blocks = (int64_t)g.N * tiles_y * tiles_x * g.G;
-        if (blocks < ((int64_t)1 << 31) && 2 * items < ((int64_t)1 << 32) - 256) {
 #define MTP_DCN_GATHER(R_, OS3_) launch_bwd_gather<T, R_, OS3_>(input, offset, mask, grad_output, grad_input, grad_offset, grad_mask, g, s, tiles_x, tiles_y, blocks, items)
-            // default: the window form.  The 3 x 3 form is 8 % faster for offsets below a pixel (a freshly initialised network: the offset head starts at
-            // zero) but its reach is one pixel around the nominal position -- with offsets of sigma = 0.5 ... 1.6 px (bench.py re-draws the heads like
-            // fixture f12) 13 ... 77 % of the samples leave it and go through the atomics: InternImage-XL step 72.7 vs 69.1 ms (same box).
-            if (g.kh == 3 && g.kw == 3 && g.dh == 1 && g.dw == 1 && g.form3x3_bwd) {
-                if (g.os == 1.0f) return MTP_DCN_GATHER(2, 1);
-                if (g.os == 2.0f) return MTP_DCN_GATHER(3, 2);
-            }
-            return reach <= 2 ? MTP_DCN_GATHER(2, 0) : MTP_DCN_GATHER(3, 0);
-#undef MTP_DCN_GATHER
+        switch (fam) {
+            case MTP_DCNV3_BWD_3X3_OS1: return MTP_DCN_GATHER(2, 1);
+            case MTP_DCNV3_BWD_3X3_OS2: return MTP_DCN_GATHER(3, 2);
+            case MTP_DCNV3_BWD_WINDOW_R2: return MTP_DCN_GATHER(2, 0);
+            default: return MTP_DCN_GATHER(3, 0);
         }
+#undef MTP_DCN_GATHER
     }
-    if (g.goff_act) return MTP_ERR_UNSUPPORTED;      // (the operand copy exists in the gather form only; the caller casts grad_offset itself)
     hipError_t e = hipMemsetAsync(grad_input, 0, sizeof(float) * (size_t)g.N * g.H * g.W * g.G * g.GC, s);   // the reference's at::zeros_like (dcnv3_cuda.cu:131)
     if (e != hipSuccess) return (int)e;
     if (!shfl) {
@@ -879,61 +900,69 @@ int launch_bwd(const void* input, const void* offset, const void* mask, const vo
     return mtp_launch_status();
 }
 
+// Every decision the entry points below take before they launch -- geometry, pointers, dtype, the size limit, the kernel family -- in one function that
+// mtp_dcnv3_kernel calls too: < 0 = the error to return, MTP_DCNV3_KERNEL_NONE = MTP_ERR_UNSUPPORTED, else the family to launch (g filled in).
+// f64: the entry point has a double path (fwd, bwd; not bwd_act); act: mtp_dcnv3_bwd_act, whose operand copy exists in the gather form only.
+int dcn_decide(const void* input, const void* offset, const void* mask, const void* out, const float* grad_input, const float* grad_offset, const float* grad_mask,
+               int dtype, const mtp_dcnv3_geom* geom, bool backward, bool f64, bool act, DcnGeom& g) {
+    const int rc = make_geom(geom, g);
+    if (rc) return rc == MTP_ERR_UNSUPPORTED ? (int)MTP_DCNV3_KERNEL_NONE : rc;
+    MTP_CHECK_ARG(input && offset && mask && out && (!backward || (grad_input && grad_offset && grad_mask)));
+    MTP_CHECK_ARG(dtype == MTP_F32 || dtype == MTP_BF16 || (f64 && dtype == MTP_F64));
+    if (dtype == MTP_F64 && !backward) return MTP_DCNV3_F64;      // (one lane per element, 64-bit indices: no size limit)
+    if ((int64_t)g.N * g.Ho * g.Wo * g.G * g.GC >= ((int64_t)1 << 32) - 256) return MTP_DCNV3_KERNEL_NONE;   // one lane per element at most
+    if (dtype == MTP_F64) return MTP_DCNV3_F64;
+    if (!backward) return fwd_family(input, offset, out, g);
+    const int fam = bwd_family(input, out, grad_input, grad_offset, g);
+    if (act && (fam == MTP_DCNV3_BWD_SCATTER_SHFL || fam == MTP_DCNV3_BWD_SCATTER_ATOMIC)) return MTP_DCNV3_KERNEL_NONE;   // (the caller casts grad_offset itself)
+    return fam;
+}
+
 }  // namespace
 
-extern "C" int mtp_dcnv3_out_size(const mtp_dcnv3_geom* geom, int64_t* Ho, int64_t* Wo) {
+extern "C" int mtp_dcnv3_kernel(const void* input, const void* offset, const void* mask, const void* out, const float* grad_input, const float* grad_offset,
+                                const float* grad_mask, int dtype, const mtp_dcnv3_geom* geom, int backward) {
     DcnGeom g;
-    const int rc = make_geom(geom, g);
-    if (rc) return rc;
-    MTP_CHECK_ARG(Ho && Wo);
-    *Ho = g.Ho;
-    *Wo = g.Wo;
-    return 0;
+    return dcn_decide(input, offset, mask, out, grad_input, grad_offset, grad_mask, dtype, geom, backward != 0, true, false, g);
 }
 
 extern "C" int mtp_dcnv3_fwd(const void* input, const void* offset, const void* mask, void* output, int dtype, const mtp_dcnv3_geom* geom, mtp_stream_t stream) {
     DcnGeom g;
-    const int rc = make_geom(geom, g);
-    if (rc) return rc;
-    MTP_CHECK_ARG(input && offset && mask && output);
-    if (dtype == MTP_F64) {
+    const int fam = dcn_decide(input, offset, mask, output, nullptr, nullptr, nullptr, dtype, geom, false, true, false, g);
+    if (fam < 0) return fam;
+    if (fam == MTP_DCNV3_KERNEL_NONE) return MTP_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    if (fam == MTP_DCNV3_F64) {
         const int64_t total = (int64_t)g.N * g.Ho * g.Wo * g.G * g.GC;
-        hipLaunchKernelGGL(dcnv3_f64_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const double*)input, (const double*)offset,
+        hipLaunchKernelGGL(dcnv3_f64_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const double*)input, (const double*)offset,
                            (const double*)mask, (const double*)nullptr, (double*)output, (double*)nullptr, (double*)nullptr, (double*)nullptr, g, total);
         return mtp_launch_status();
     }
-    MTP_CHECK_ARG(dtype == MTP_F32 || dtype == MTP_BF16);
-    if ((int64_t)g.N * g.Ho * g.Wo * g.G * g.GC >= ((int64_t)1 << 32) - 256) return MTP_ERR_UNSUPPORTED;   // one lane per element at most
-    hipStream_t s = (hipStream_t)stream;
-    return dtype == MTP_F32 ? launch_fwd<float>(input, offset, mask, output, g, s) : launch_fwd<bf16_t>(input, offset, mask, output, g, s);
+    return dtype == MTP_F32 ? launch_fwd<float>(input, offset, mask, output, g, fam, s) : launch_fwd<bf16_t>(input, offset, mask, output, g, fam, s);
 }
 
 extern "C" int mtp_dcnv3_bwd_act(const void* input, const void* offset, const void* mask, const void* grad_output, int dtype, float* grad_input, float* grad_offset,
                                  float* grad_mask, void* grad_offset_act, int64_t act_ld, const mtp_dcnv3_geom* geom, mtp_stream_t stream) {
     DcnGeom g;
-    const int rc = make_geom(geom, g);
-    if (rc) return rc;
-    MTP_CHECK_ARG(input && offset && mask && grad_output && grad_input && grad_offset && grad_mask && grad_offset_act);
-    MTP_CHECK_ARG(dtype == MTP_F32 || dtype == MTP_BF16);
-    MTP_CHECK_ARG(act_ld >= (int64_t)g.G * g.P * 2 && act_ld < ((int64_t)1 << 30));
-    if ((int64_t)g.N * g.Ho * g.Wo * g.G * g.GC >= ((int64_t)1 << 32) - 256) return MTP_ERR_UNSUPPORTED;
+    const int fam = dcn_decide(input, offset, mask, grad_output, grad_input, grad_offset, grad_mask, dtype, geom, true, false, true, g);
+    if (fam < 0) return fam;
+    MTP_CHECK_ARG(grad_offset_act && act_ld >= (int64_t)g.G * g.P * 2 && act_ld < ((int64_t)1 << 30));
+    if (fam == MTP_DCNV3_KERNEL_NONE) return MTP_ERR_UNSUPPORTED;
     g.goff_act = grad_offset_act;
     g.goff_act_ld = (int)act_ld;
     hipStream_t s = (hipStream_t)stream;
-    return dtype == MTP_F32 ? launch_bwd<float>(input, offset, mask, grad_output, grad_input, grad_offset, grad_mask, g, s)
-                            : launch_bwd<bf16_t>(input, offset, mask, grad_output, grad_input, grad_offset, grad_mask, g, s);
+    return dtype == MTP_F32 ? launch_bwd<float>(input, offset, mask, grad_output, grad_input, grad_offset, grad_mask, g, fam, s)
+                            : launch_bwd<bf16_t>(input, offset, mask, grad_output, grad_input, grad_offset, grad_mask, g, fam, s);
 }
 
 extern "C" int mtp_dcnv3_bwd(const void* input, const void* offset, const void* mask, const void* grad_output, int dtype, float* grad_input, float* grad_offset,
                              float* grad_mask, const mtp_dcnv3_geom* geom, mtp_stream_t stream) {
     DcnGeom g;
-    const int rc = make_geom(geom, g);
-    if (rc) return rc;
-    MTP_CHECK_ARG(input && offset && mask && grad_output && grad_input && grad_offset && grad_mask);
-    MTP_CHECK_ARG(dtype == MTP_F32 || dtype == MTP_BF16 || dtype == MTP_F64);
-    if ((int64_t)g.N * g.Ho * g.Wo * g.G * g.GC >= ((int64_t)1 << 32) - 256) return MTP_ERR_UNSUPPORTED;
+    const int fam = dcn_decide(input, offset, mask, grad_output, grad_input, grad_offset, grad_mask, dtype, geom, true, true, false, g);
+    if (fam < 0) return fam;
+    if (fam == MTP_DCNV3_KERNEL_NONE) return MTP_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == MTP_F64) {      // (the three gradient pointers are double buffers here, see mtp_hip.h)
+    if (fam == MTP_DCNV3_F64) {      // (the three gradient pointers are double buffers here, see mtp_hip.h)
         const int64_t items = (int64_t)g.N * g.Ho * g.Wo * g.G, total = items * g.GC;
         hipError_t e = hipMemsetAsync(grad_input, 0, sizeof(double) * (size_t)g.N * g.H * g.W * g.G * g.GC, s);
         if (e == hipSuccess) e = hipMemsetAsync(grad_offset, 0, sizeof(double) * (size_t)items * 2 * g.P, s);
@@ -944,6 +973,16 @@ extern "C" int mtp_dcnv3_bwd(const void* input, const void* offset, const void* 
                            reinterpret_cast<double*>(grad_mask), g, total);
         return mtp_launch_status();
     }
-    return dtype == MTP_F32 ? launch_bwd<float>(input, offset, mask, grad_output, grad_input, grad_offset, grad_mask, g, s)
-                            : launch_bwd<bf16_t>(input, offset, mask, grad_output, grad_input, grad_offset, grad_mask, g, s);
+    return dtype == MTP_F32 ? launch_bwd<float>(input, offset, mask, grad_output, grad_input, grad_offset, grad_mask, g, fam, s)
+                            : launch_bwd<bf16_t>(input, offset, mask, grad_output, grad_input, grad_offset, grad_mask, g, fam, s);
+}
+
+extern "C" int mtp_dcnv3_out_size(const mtp_dcnv3_geom* geom, int64_t* Ho, int64_t* Wo) {
+    DcnGeom g;
+    const int rc = make_geom(geom, g);
+    if (rc) return rc;
+    MTP_CHECK_ARG(Ho && Wo);
+    *Ho = g.Ho;
+    *Wo = g.Wo;
+    return 0;
 }

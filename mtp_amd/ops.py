@@ -870,6 +870,28 @@ def col2im3x3(dcols, dx, strides, N, H, W, Cin, stride, accumulate=False):
     return dx
 
 
+# kernel families of the operators below that have more than one kernel, as include/mtp_hip.h names them (MTP_CONV_KERNEL_*; 0 = the entry point
+# would refuse the call as unsupported)
+CONV_KERNEL = {"element": 1, "v8": 2, "p8": 3, "px4": 4}
+_CONV_OP = {"im2col3x3": 0, "col2im3x3": 1, "dwconv3x3_fwd": 2, "dwconv3x3_bwd_dx": 3, "dwconv3x3_bwd_dw": 4}
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def conv_kernel(op, src, dst, N, H, W, Cc, strides=(0, 0, 0, 0), stride=1, Kp=0, w=None, b=None):
+    """the kernel `op` (a key of _CONV_OP) runs for these very tensors and sizes (a CONV_KERNEL value): the decision the entry point launches by; no launch,
+    no device.  src / dst: the operator's source and destination (im2col3x3: x, cols; col2im3x3: dcols, dx; dwconv3x3_fwd: x, y; _bwd_dx: dy, dx;
+    _bwd_dw: dy, the partials or None = the wrapper's own 16-byte aligned workspace); Cc = Cin for the two gathers"""
+    dptr = 16 if (dst is None and op == "dwconv3x3_bwd_dw") else _ptr(dst)
+    sN, sH, sW, sC = strides
+    rc = lib().mtp_conv_kernel(_CONV_OP[op], _ptr(src), _dt(src), sN, sH, sW, sC, dptr, _dt(dst) if dst is not None else 0, _ptr(w), _ptr(b), N, H, W, Cc, stride, Kp)
+    if rc < 0:
+        check(rc, "mtp_conv_kernel")
+    return rc
+
+
 def conv3x3_pack(w, w2, w2t):
     Cout, Cin = w.shape[:2]
     img = w2 if w2 is not None else w2t

@@ -127,6 +127,24 @@ def dcnv3_backward_act(input, offset, mask, kernel_h, kernel_w, stride_h, stride
     return [grad_input, grad_offset, grad_mask, act]
 
 
+# kernel families, as include/mtp_hip.h names them (MTP_DCNV3_*; 0 = the entry point would refuse the geometry as unsupported)
+DCNV3_KERNEL = {"fwd9": 1, "fwd_vec8": 2, "fwd_scalar": 3, "f64": 4, "bwd_window_r2": 5, "bwd_window_r3": 6, "bwd_3x3_os1": 7, "bwd_3x3_os2": 8,
+                "bwd_scatter_shfl": 9, "bwd_scatter_atomic": 10}
+
+
+def dcnv3_kernel(input, offset, mask, out, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, group_channels, offset_scale,
+                 im2col_step, remove_center=0, grads=None):
+    """the kernels dcnv3_forward (grads None; out = the output buffer) resp. dcnv3_backward (out = grad_output, grads = the three gradient buffers) run for
+    these very tensors (a DCNV3_KERNEL value): the decision the entry points launch by, MTP_DCNV3_VARIANT included; no launch, no device"""
+    g = _geom(input, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, group_channels, offset_scale, im2col_step, remove_center)
+    gp = [t.data_ptr() for t in grads] if grads is not None else [None, None, None]
+    rc = lib().mtp_dcnv3_kernel(input.data_ptr(), offset.data_ptr(), mask.data_ptr(), out.data_ptr(), gp[0], gp[1], gp[2], _dtc(input), C.byref(g),
+                                int(grads is not None))
+    if rc < 0:
+        _lib.check(rc, "mtp_dcnv3_kernel")
+    return rc
+
+
 class DCNv3Function(Function):
     """functions/dcnv3_func.py:22-77 -- same apply() arguments; the saved tensors and the 13 `None` gradients too."""
 

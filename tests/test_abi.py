@@ -43,6 +43,38 @@ def test_gemm_variant_flags_mirror_the_header():
     assert fields == [f for f, _ in _lib.GemmNtPlan._fields_] and C.sizeof(_lib.GemmNtPlan) == 4 * len(fields)
 
 
+def test_conv_and_dcnv3_kernel_queries_mirror_the_header():
+    """enum mtp_conv_op / mtp_conv_kernel_family / mtp_dcnv3_kernel_family against their mirrors in _lib and the name tables of ops / ops_dcnv3; the two
+    queries are stream-less host functions that refuse NULL pointers, a NULL geometry and an unknown operator like the entry points they speak for"""
+    import ctypes as C
+    from mtp_amd import _lib, ops
+    from mtp_amd.ops_dcnv3 import DCNV3_KERNEL
+    src = open(os.path.join(ROOT, "include", "mtp_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    for enum, prefix, count in (("mtp_conv_op", "CONV_OP_", 5), ("mtp_conv_kernel_family", "CONV_KERNEL_", 5), ("mtp_dcnv3_kernel_family", "DCNV3_", 11)):
+        body = re.search(r"typedef enum \{([^}]*)\}\s*%s;" % enum, src).group(1)
+        items = re.findall(r"MTP_([A-Z0-9_]+)\s*=\s*(\d+)\s*(?:,|$)", body)
+        assert len(items) == count == body.count("="), enum
+        for name, v in items:
+            assert name.startswith(prefix) and getattr(_lib, name) == int(v), name
+        assert sorted(n for n in dir(_lib) if n.startswith(prefix)) == sorted(n for n, _ in items), enum
+    assert ops.CONV_KERNEL == {n[len("CONV_KERNEL_"):].lower(): getattr(_lib, n) for n in dir(_lib) if n.startswith("CONV_KERNEL_") and n != "CONV_KERNEL_NONE"}
+    assert DCNV3_KERNEL == {n[len("DCNV3_"):].lower(): getattr(_lib, n) for n in dir(_lib) if n.startswith("DCNV3_") and n != "DCNV3_KERNEL_NONE"}
+    assert sorted(ops._CONV_OP.values()) == [0, 1, 2, 3, 4]
+    for name in ("mtp_conv_kernel", "mtp_dcnv3_kernel"):
+        assert C.c_void_p not in _lib.SIGNATURES[name][1][-1:], name        # no trailing stream argument
+    lib = _lib.load()
+    g = _lib.Dcnv3Geom(N=1, H=4, W=4, kernel_h=3, kernel_w=3, stride_h=1, stride_w=1, pad_h=1, pad_w=1, dilation_h=1, dilation_w=1, group=1, group_channels=16,
+                       offset_scale=1.0, im2col_step=1)
+    assert lib.mtp_dcnv3_kernel(16, 16, 16, 16, None, None, None, 0, C.byref(g), 0) == _lib.DCNV3_FWD9
+    assert lib.mtp_dcnv3_kernel(16, 16, 16, 16, None, None, None, 0, C.byref(g), 1) == -1          # backward without the gradient buffers
+    assert lib.mtp_dcnv3_kernel(16, 16, 16, 16, None, None, None, 0, None, 0) == -1 and lib.mtp_dcnv3_kernel(16, 16, 16, 16, None, None, None, 7, C.byref(g), 0) == -1
+    assert lib.mtp_dcnv3_kernel(16, 16, 16, 16, 16, 16, 16, 2, C.byref(g), 1) == _lib.DCNV3_F64
+    assert lib.mtp_conv_kernel(9, 16, 0, 0, 0, 0, 0, 16, 0, 16, None, 1, 1, 1, 4, 1, 0) == -1       # unknown operator
+    assert lib.mtp_conv_kernel(_lib.CONV_OP_DWCONV3X3_FWD, 16, 1, 0, 0, 0, 0, 16, 1, 16, None, 1, 1, 8, 4, 1, 0) == _lib.CONV_KERNEL_P8
+    assert lib.mtp_conv_kernel(_lib.CONV_OP_DWCONV3X3_FWD, 16, 2, 0, 0, 0, 0, 16, 2, 16, None, 1, 1, 8, 4, 1, 0) == _lib.CONV_KERNEL_NONE      # f64: unsupported
+
+
 def test_gemm_args_struct_layout():
     import ctypes as C
     from mtp_amd._lib import GemmArgs
