@@ -569,6 +569,24 @@ int mtp_seg_ce(const void* logits, int dtype, int64_t ld, int64_t N, int64_t h, 
                int64_t W, int ignore_index, float loss_weight, float* loss, float* dlogits, int64_t ldd, void* workspace, int64_t workspace_bytes,
                mtp_stream_t stream);
 
+/* ---- segmentation evaluation (mmseg EncoderDecoder.slide_inference + IoUMetric; csrc/seg_eval.hip) ---------------------
+ * Sliding-window inference: logits (N*h*w, ld) ACT, K classes (ld >= K rounded up to 4, the columns K .. read but never compared), resized bilinearly
+ * (align_corners=False, the index rule and operation order of mtp_resize_bilinear_fwd) to the crop (Hc, Wc) and ADDED into the f32 accumulator acc
+ * (N, H, W) x lda at the window origin (y1, x1): preds += F.pad(crop_seg_logit, ...) without the padded temporary.  One launch per window position
+ * covers all N images; windows follow each other in stream order, so there are no atomics.  The caller zeroes acc before the first window. */
+int mtp_seg_window_accumulate(const void* logits, int dtype, int64_t ld, int64_t N, int64_t h, int64_t w, int64_t K, float* acc, int64_t lda,
+                              int64_t H, int64_t W, int64_t y1, int64_t x1, int64_t Hc, int64_t Wc, mtp_stream_t stream);
+/* One pass over acc: v = acc / (cy[y] * cx[x]) (the windows form a grid product, so the count is separable; cy (H) / cx (W) int32 >= 1, both NULL = 1),
+ * arg-max over the first K <= 256 columns (ties to the lowest class, torch.argmax's rule) -> pred (N, H, W) uint8 (or NULL); v -> seg_logits (N, K, H, W)
+ * f32 NCHW (or NULL); write_back: v back into acc (the divided rows, for a resize that follows).  With labels (N, H, W) uint8 / int64 (label_bytes 1 / 8)
+ * and areas: areas[3][K] int64 += (intersect, pred, label) histograms over the pixels whose label is not ignore_index (per-workgroup int32 counters
+ * in LDS, 64-bit integer atomic adds: exact and order-independent).  Precondition: every label is ignore_index or in [0, K) (mtp_amd.ops checks). */
+int mtp_seg_argmax_areas(float* acc, int64_t lda, int64_t N, int64_t H, int64_t W, int64_t K, const int32_t* cy, const int32_t* cx, int write_back,
+                         uint8_t* pred, float* seg_logits, const void* labels, int label_bytes, int ignore_index, int64_t* areas, mtp_stream_t stream);
+/* the same histograms from an existing prediction: pred / labels (pixels) uint8 or int64 (pred_bytes / label_bytes 1 / 8), pred in [0, K) */
+int mtp_seg_areas(const void* pred, int pred_bytes, const void* labels, int label_bytes, int64_t pixels, int64_t K, int ignore_index, int64_t* areas,
+                  mtp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -169,6 +169,9 @@ SIGNATURES = {
     "mtp_channel_scale": (i32, [p, i32, i64, p, i64, p, i32, i64, i64, i64, p]),
     "mtp_seg_ce_workspace_bytes": (i64, [i64, i64, i64, i64]),
     "mtp_seg_ce": (i32, [p, i32, i64, i64, i64, i64, i64, p, i32, i64, i64, i32, f32, p, p, i64, p, i64, p]),
+    "mtp_seg_window_accumulate": (i32, [p, i32, i64, i64, i64, i64, i64, p, i64, i64, i64, i64, i64, i64, i64, p]),
+    "mtp_seg_argmax_areas": (i32, [p, i64, i64, i64, i64, i64, p, p, i32, p, p, p, i32, i32, p, p]),
+    "mtp_seg_areas": (i32, [p, i32, p, i32, i64, i64, i32, p, p]),
     "mtp_version": (C.c_char_p, []),
     "mtp_stream_create_low_priority": (i32, [p]),
     "mtp_stream_create_cu_mask": (i32, [p, i32, p]),

@@ -3,6 +3,7 @@
 // concatenation in place.  Statistics and reductions are f32 and deterministic: per-workgroup partial rows summed in a fixed order
 // (col_sums_kernel, or the single-workgroup tree of the loss), no float atomics anywhere in this file.
 #include "common.h"
+#include "resize_common.h"
 
 namespace {
 
@@ -187,23 +188,7 @@ __global__ void __launch_bounds__(kThreads) bn_bwd_dx_kernel(const void* dy, int
 }
 
 // ---------------------------------------------------------------------------------------------------------------- bilinear resize
-// F.interpolate(mode='bilinear', align_corners=False) index rule (ATen area_pixel_compute_source_index): src = max(scale * (o + 0.5) - 0.5, 0),
-// scale = in / out, i0 = (int)src, i1 = i0 + (i0 < in - 1), weights (1 - l, l) with l = src - i0.
-struct Lin {
-    int i0, i1;
-    float w0, w1;
-};
-__device__ __forceinline__ Lin lin_index(int o, int in, float scale) {
-    float src = scale * ((float)o + 0.5f) - 0.5f;
-    src = src < 0.0f ? 0.0f : src;
-    Lin L;
-    L.i0 = (int)src;
-    if (L.i0 > in - 1) L.i0 = in - 1;
-    L.i1 = L.i0 + (L.i0 < in - 1 ? 1 : 0);
-    L.w1 = src - (float)L.i0;
-    L.w0 = 1.0f - L.w1;
-    return L;
-}
+// Lin / lin_index (the F.interpolate align_corners=False index rule): resize_common.h, shared with seg_eval.hip
 // weight of source index i in output o's interpolation
 __device__ __forceinline__ float lin_weight(int o, int i, int in, float scale) {
     const Lin L = lin_index(o, in, scale);

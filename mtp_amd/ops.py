@@ -1117,3 +1117,82 @@ def seg_ce(logits, K, N, h, w, labels, ignore_index=255, loss_weight=1.0):
     check(lib().mtp_seg_ce(_p(logits), _dt(logits), ld, N, h, w, K, _p(labels), labels.element_size(), H, W, int(ignore_index), float(loss_weight), _p(loss),
                            _p(dlogits), ld, _p(ws), ws.numel() * 4, _s()), "mtp_seg_ce")
     return loss, dlogits
+
+
+# ------------------------------------------------------------------------------------------------ segmentation evaluation (csrc/seg_eval.hip)
+SEG_MAX_CLASSES = 256      # the arg-max / area kernels keep 3 x K counters per workgroup in LDS
+
+
+def _acc_pitch(acc, K):
+    """pixel pitch of an accumulator (N, H, W, C >= K rounded up to 4) f32: contiguous, or the leading columns of a wider contiguous map"""
+    assert acc.dim() == 4 and acc.dtype == torch.float32 and acc.stride(3) == 1 and acc.shape[3] >= (K + 3) // 4 * 4
+    lda = acc.stride(2)
+    assert lda >= acc.shape[3] and acc.stride(1) == acc.shape[2] * lda and acc.stride(0) == acc.shape[1] * acc.shape[2] * lda
+    return lda
+
+
+def _check_classes(name, t, K, ignore_index=None):
+    """every value in [0, K) (or ignore_index): the kernels index LDS counters with them"""
+    if t.dtype not in (torch.uint8, torch.int64) or not t.is_contiguous():
+        raise TypeError("%s must be a contiguous uint8 / int64 tensor" % name)
+    keep = torch.ones_like(t, dtype=torch.bool) if ignore_index is None else (t != ignore_index)
+    bad = (keep & (t.long() >= K)).any()         # (uint8: only the upper bound can fail)
+    if t.dtype == torch.int64:
+        bad = bad | (keep & (t < 0)).any()
+    if bool(bad):
+        raise ValueError("%s outside [0, %d)%s" % (name, K, "" if ignore_index is None else " that are not ignore_index (%d)" % ignore_index))
+
+
+def _check_areas(areas, K):
+    if K > SEG_MAX_CLASSES:
+        raise ValueError("at most %d classes (got %d)" % (SEG_MAX_CLASSES, K))
+    assert areas.dtype == torch.int64 and areas.shape == (3, K) and areas.is_contiguous()
+
+
+def seg_window_accumulate(logits, K, N, h, w, acc, y1, x1, Hc, Wc):
+    """acc[:, y1:y1 + Hc, x1:x1 + Wc, :K] += bilinear resize of logits (N*h*w, ld >= K rounded up to 4) ACT to (Hc, Wc); acc (N, H, W, >= K) f32"""
+    lda = _acc_pitch(acc, K)
+    assert logits.shape[0] == N * h * w and acc.shape[0] == N
+    H, W = acc.shape[1:3]
+    if y1 < 0 or x1 < 0 or y1 + Hc > H or x1 + Wc > W:
+        raise ValueError("window (%d, %d) + (%d, %d) outside the %d x %d map" % (y1, x1, Hc, Wc, H, W))
+    check(lib().mtp_seg_window_accumulate(_pv(logits), _dt(logits), _ld(logits), N, h, w, K, _pv(acc), lda, H, W, y1, x1, Hc, Wc, _s()),
+          "mtp_seg_window_accumulate")
+    return acc
+
+
+def seg_argmax_areas(acc, K, cy=None, cx=None, pred=None, seg_logits=None, labels=None, areas=None, ignore_index=255, write_back=False):
+    """one pass over acc (N, H, W, >= K) f32: / (cy[y] * cx[x]) (int32 window counts; None = 1), arg-max over the first K columns -> pred (N, H, W) uint8,
+    the divided values -> seg_logits (N, K, H, W) f32 and / or back into acc (write_back); with labels (N, H, W) uint8 / int64 and areas (3, K) int64:
+    areas += (intersect, pred, label) histograms over the pixels whose label is not ignore_index.  Any output may be None."""
+    if K > SEG_MAX_CLASSES:
+        raise ValueError("at most %d classes (got %d)" % (SEG_MAX_CLASSES, K))
+    lda = _acc_pitch(acc, K)
+    N, H, W = acc.shape[:3]
+    if (cy is None) != (cx is None) or (labels is None) != (areas is None):
+        raise ValueError("cy and cx, labels and areas go together")
+    if cy is not None:
+        assert cy.dtype == torch.int32 and cx.dtype == torch.int32 and cy.shape == (H,) and cx.shape == (W,)
+    if pred is not None:
+        assert pred.dtype == torch.uint8 and pred.shape == (N, H, W)
+    if seg_logits is not None:
+        assert seg_logits.dtype == torch.float32 and seg_logits.shape == (N, K, H, W)
+    if labels is not None:
+        assert labels.shape == (N, H, W)
+        _check_classes("labels", labels, K, ignore_index)
+        _check_areas(areas, K)
+    check(lib().mtp_seg_argmax_areas(_pv(acc), lda, N, H, W, K, _p(cy), _p(cx), int(write_back), _p(pred), _p(seg_logits), _p(labels),
+                                     0 if labels is None else labels.element_size(), int(ignore_index), _p(areas), _s()), "mtp_seg_argmax_areas")
+    return pred
+
+
+def seg_areas(pred, labels, K, areas, ignore_index=255):
+    """areas (3, K) int64 += (intersect, pred, label) histograms of an existing prediction; pred / labels: same shape, uint8 or int64"""
+    _check_areas(areas, K)
+    if pred.shape != labels.shape:
+        raise ValueError("pred %s and labels %s differ in shape" % (tuple(pred.shape), tuple(labels.shape)))
+    _check_classes("pred", pred, K)
+    _check_classes("labels", labels, K, ignore_index)
+    check(lib().mtp_seg_areas(_p(pred), pred.element_size(), _p(labels), labels.element_size(), pred.numel(), K, int(ignore_index), _p(areas), _s()),
+          "mtp_seg_areas")
+    return areas
