@@ -587,6 +587,27 @@ int mtp_seg_argmax_areas(float* acc, int64_t lda, int64_t N, int64_t H, int64_t 
 int mtp_seg_areas(const void* pred, int pred_bytes, const void* labels, int label_bytes, int64_t pixels, int64_t K, int ignore_index, int64_t* areas,
                   mtp_stream_t stream);
 
+/* ---- change detection: pair fusion and the UNet decoder's block input (open-cd FeatureFusionNeck / UNetHead; csrc/unet_head.hip) ----------------
+ * mtp_fuse_pair_fwd: f (2N, C, H, W) NCHW, f32 or bf16, the backbone's map of the 2N-batch ("from" images first, "to" images last) -> the fused
+ * channels-last rows out (N*H*W, ld) of the N pairs, the layout change and the fusion in one pass: sum = x1 + x2, diff = x2 - x1, abs_diff = |x1 - x2|
+ * in C columns, concat = [x1 | x2] in 2C columns.  C a multiple of 4; ld a multiple of 4 (out may be a column slice of a wider map).
+ * mtp_fuse_pair_bwd: g (N*H*W, ldg) f32 row gradient -> df (2N, C, H, W) f32, both halves, every element written.  abs_diff: +-sign(x1 - x2) g with
+ * the sign recomputed from the saved inputs f (sign(0) = 0, torch's abs rule); f is read for abs_diff only (NULL otherwise). */
+typedef enum { MTP_FUSE_CONCAT = 0, MTP_FUSE_SUM = 1, MTP_FUSE_DIFF = 2, MTP_FUSE_ABS_DIFF = 3 } mtp_fuse_policy;
+int mtp_fuse_pair_fwd(const void* f, int f_dtype, void* out, int out_dtype, int64_t ld, int64_t N, int64_t C, int64_t H, int64_t W, int policy,
+                      mtp_stream_t stream);
+int mtp_fuse_pair_bwd(const float* g, int64_t ldg, const void* f, int f_dtype, float* df, int64_t N, int64_t C, int64_t H, int64_t W, int policy,
+                      mtp_stream_t stream);
+/* One decoder block's conv input y (N*2h*2w, ldy >= Cx + Cs), written once: columns [0, Cx) = x (N*h*w, ldx) nearest x2 (source pixel (oy >> 1,
+ * ox >> 1)); columns [Cx, Cx + Cs) = skip (N*hs*ws, lds) resized bilinearly to 2h x 2w (align_corners=False, mtp_resize_bilinear_fwd's index rule and
+ * operation order; plain copies when hs x ws is 2h x 2w already).  x and skip share in_dtype.  skip NULL or Cs 0: the skip-less block.
+ * The backward takes the f32 gradient dy of that input (what mtp_col2im3x3 writes): dx (N*h*w, lddx) f32 = / += the four children summed in a fixed
+ * order; dskip (N*hs*ws, ldds) f32 = / += the bilinear adjoint gather on the column slice (dskip NULL or Cs 0: none). */
+int mtp_unet_up_cat_fwd(const void* x, int64_t ldx, int64_t Cx, const void* skip, int64_t lds, int64_t Cs, int in_dtype, void* y, int y_dtype, int64_t ldy,
+                        int64_t N, int64_t h, int64_t w, int64_t hs, int64_t ws, mtp_stream_t stream);
+int mtp_unet_up_cat_bwd(const float* dy, int64_t lddy, float* dx, int64_t lddx, int64_t Cx, float* dskip, int64_t ldds, int64_t Cs, int64_t N, int64_t h,
+                        int64_t w, int64_t hs, int64_t ws, int accumulate, mtp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

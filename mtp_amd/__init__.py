@@ -47,8 +47,9 @@ def hw_queue_note():
 from .backbone import (InternImage, internimage_xl, RVSA_MTP, RVSA_MTP_branches, RVSA_MTP_det, RVSA_MTP_taps, ViT_Win_RVSA_V3_WSZ7, vit_b_rvsa, vit_l_rvsa,  # noqa: F401
                        window_partition, window_reverse)
 from .registry import BACKBONES, MODELS, build_backbone  # noqa: F401
-from .decode_heads import UPerHead  # noqa: F401
-from .segmentors import EncoderDecoder  # noqa: F401
+from .decode_heads import UNetHead, UPerHead  # noqa: F401
+from .necks import FeatureFusionNeck  # noqa: F401
+from .segmentors import EncoderDecoder, SiamEncoderDecoder  # noqa: F401
 from .evaluation import IoUMetric  # noqa: F401
 
 __version__ = "0.6.0"      # = mtp_version() of libmtp_hip.so ("mtp_hip 0.6 (gfx950)"): the round of the build

@@ -32,6 +32,9 @@ CONV_KERNEL_NONE, CONV_KERNEL_ELEMENT, CONV_KERNEL_V8, CONV_KERNEL_P8, CONV_KERN
 DCNV3_KERNEL_NONE, DCNV3_FWD9, DCNV3_FWD_VEC8, DCNV3_FWD_SCALAR, DCNV3_F64 = 0, 1, 2, 3, 4
 DCNV3_BWD_WINDOW_R2, DCNV3_BWD_WINDOW_R3, DCNV3_BWD_3X3_OS1, DCNV3_BWD_3X3_OS2, DCNV3_BWD_SCATTER_SHFL, DCNV3_BWD_SCATTER_ATOMIC = 5, 6, 7, 8, 9, 10
 
+# enum mtp_fuse_policy (mtp_fuse_pair_fwd / _bwd)
+FUSE_CONCAT, FUSE_SUM, FUSE_DIFF, FUSE_ABS_DIFF = 0, 1, 2, 3
+
 p, i64, i32, f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
 
 
@@ -172,6 +175,10 @@ SIGNATURES = {
     "mtp_seg_window_accumulate": (i32, [p, i32, i64, i64, i64, i64, i64, p, i64, i64, i64, i64, i64, i64, i64, p]),
     "mtp_seg_argmax_areas": (i32, [p, i64, i64, i64, i64, i64, p, p, i32, p, p, p, i32, i32, p, p]),
     "mtp_seg_areas": (i32, [p, i32, p, i32, i64, i64, i32, p, p]),
+    "mtp_fuse_pair_fwd": (i32, [p, i32, p, i32, i64, i64, i64, i64, i64, i32, p]),
+    "mtp_fuse_pair_bwd": (i32, [p, i64, p, i32, p, i64, i64, i64, i64, i32, p]),
+    "mtp_unet_up_cat_fwd": (i32, [p, i64, i64, p, i64, i64, i32, p, i32, i64, i64, i64, i64, i64, i64, p]),
+    "mtp_unet_up_cat_bwd": (i32, [p, i64, p, i64, i64, p, i64, i64, i64, i64, i64, i64, i64, i32, p]),
     "mtp_version": (C.c_char_p, []),
     "mtp_stream_create_low_priority": (i32, [p]),
     "mtp_stream_create_cu_mask": (i32, [p, i32, p]),

@@ -1119,6 +1119,61 @@ def seg_ce(logits, K, N, h, w, labels, ignore_index=255, loss_weight=1.0):
     return loss, dlogits
 
 
+# ------------------------------------------------------------------------------------------------ change detection (csrc/unet_head.hip)
+FUSE_POLICIES = {"concat": _lib.FUSE_CONCAT, "sum": _lib.FUSE_SUM, "diff": _lib.FUSE_DIFF, "abs_diff": _lib.FUSE_ABS_DIFF}
+
+
+def fuse_policy(policy):
+    try:
+        return FUSE_POLICIES[policy]
+    except (KeyError, TypeError):
+        raise ValueError("unknown fusion policy %r (one of %s)" % (policy, ", ".join(sorted(FUSE_POLICIES))))
+
+
+def fuse_pair_fwd(f, out, policy):
+    """f (2N, C, H, W) NCHW f32 / bf16, 'from' samples first -> out (N*H*W, C -- 2C for 'concat') channels-last (a column slice is fine)"""
+    B, Cc, H, W = f.shape
+    N = B // 2
+    assert B == 2 * N and out.shape == (N * H * W, 2 * Cc if policy == "concat" else Cc)
+    check(lib().mtp_fuse_pair_fwd(_p(f), _dt(f), _pv(out), _dt(out), _ld(out), N, Cc, H, W, fuse_policy(policy), _s()), "mtp_fuse_pair_fwd")
+    return out
+
+
+def fuse_pair_bwd(g, f, df, policy):
+    """g (N*H*W, C | 2C) f32 (a column slice is fine), f the forward's input (read for 'abs_diff' only) -> df (2N, C, H, W) f32, both halves"""
+    B, Cc, H, W = df.shape
+    N = B // 2
+    assert B == 2 * N and df.dtype == torch.float32 and g.shape == (N * H * W, 2 * Cc if policy == "concat" else Cc)
+    assert f is None or f.shape == df.shape
+    pol = fuse_policy(policy)
+    fin = f if policy == "abs_diff" else None
+    assert g.dtype == torch.float32
+    check(lib().mtp_fuse_pair_bwd(_pv(g), _ld(g), _p(fin), _dt(fin) if fin is not None else 0, _f32(df), N, Cc, H, W, pol, _s()), "mtp_fuse_pair_bwd")
+    return df
+
+
+def unet_up_cat_fwd(x, skip, y, N, h, w, hs=0, ws=0):
+    """y (N*2h*2w, Cx + Cs) = [x (N*h*w, Cx) nearest x2 | skip (N*hs*ws, Cs) resized bilinearly to 2h x 2w]; skip None: the skip-less block.
+    Column slices allowed everywhere."""
+    Cx = x.shape[1]
+    Cs = 0 if skip is None else skip.shape[1]
+    assert x.shape[0] == N * h * w and y.shape == (4 * N * h * w, Cx + Cs) and (skip is None or (skip.dtype == x.dtype and skip.shape[0] == N * hs * ws))
+    check(lib().mtp_unet_up_cat_fwd(_pv(x), _ld(x), Cx, None if skip is None else _pv(skip), 0 if skip is None else _ld(skip), Cs, _dt(x), _pv(y), _dt(y),
+                                    _ld(y), N, h, w, hs, ws, _s()), "mtp_unet_up_cat_fwd")
+    return y
+
+
+def unet_up_cat_bwd(dy, dx, dskip, N, h, w, hs=0, ws=0, accumulate=False):
+    """dy (N*2h*2w, Cx + Cs) f32 -> dx (N*h*w, Cx) f32 and dskip (N*hs*ws, Cs) f32 (None: no skip), = / += (accumulate)"""
+    Cx = dx.shape[1]
+    Cs = 0 if dskip is None else dskip.shape[1]
+    assert dy.dtype == dx.dtype == torch.float32 and dx.shape[0] == N * h * w and dy.shape == (4 * N * h * w, Cx + Cs)
+    assert dskip is None or (dskip.dtype == torch.float32 and dskip.shape[0] == N * hs * ws)
+    check(lib().mtp_unet_up_cat_bwd(_pv(dy), _ld(dy), _pv(dx), _ld(dx), Cx, None if dskip is None else _pv(dskip), 0 if dskip is None else _ld(dskip), Cs,
+                                    N, h, w, hs, ws, int(accumulate), _s()), "mtp_unet_up_cat_bwd")
+    return dx, dskip
+
+
 # ------------------------------------------------------------------------------------------------ segmentation evaluation (csrc/seg_eval.hip)
 SEG_MAX_CLASSES = 256      # the arg-max / area kernels keep 3 x K counters per workgroup in LDS
 
