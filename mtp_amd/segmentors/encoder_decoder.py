@@ -10,9 +10,9 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..decode_heads.uper_head import _params
-from ..engine_uper import F32, UperEngine
 from ..registry import MODELS
+
+F32 = torch.float32
 
 
 def slide_origins(size, crop, stride):
@@ -70,17 +70,8 @@ class EncoderDecoder(nn.Module):
         return self.backbone(inputs)
 
     def encode_decode(self, inputs):
-        """-> (logits (N*h*w, Kp) f32 rows on the head's 1/4 grid, columns K .. Kp zero; (N, h, w)): the head's eval-mode schedule, no NCHW round trip"""
-        head = self.decode_head
-        ins = head._transform_inputs(list(self.extract_feat(inputs)))
-        head._check_inputs(ins)
-        eng = UperEngine(head, head.precision)
-        xs = [eng.to_rows(f) for f in ins]
-        shapes = [(int(f.shape[0]), int(f.shape[2]), int(f.shape[3])) for f in ins]
-        feat, _ = eng.forward_feature(xs, shapes, _params(head), False, None)
-        N, h, w = shapes[0]
-        logits, _ = eng.cls_fwd(feat, N, h * w, "conv_seg.weight", "conv_seg.bias", None)
-        return logits, (N, h, w)
+        """-> (logits (N*h*w, Kp) f32 rows on the head's output grid, columns K .. Kp zero; (N, h, w)): the head's eval-mode schedule, no NCHW round trip"""
+        return self.decode_head.logit_rows(self.extract_feat(inputs))
 
     def whole_inference(self, inputs):
         """-> (acc (N, H, W, Kp) f32: the logits resized to the image, None, None)"""

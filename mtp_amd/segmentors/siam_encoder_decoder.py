@@ -37,10 +37,3 @@ class SiamEncoderDecoder(EncoderDecoder):
             return self.neck.forward_batch(feats)
         N = inputs.shape[0]
         return self.neck([f[:N] for f in feats], [f[N:] for f in feats])
-
-    def encode_decode(self, inputs):
-        """-> (logits (N*h*w, Kp) f32 rows on the head's output grid, (N, h, w)): the head's eval-mode schedule"""
-        return self.decode_head.logit_rows(self.extract_feat(inputs))
-
-    def loss(self, inputs, labels):
-        return self.decode_head.loss(self.extract_feat(inputs), labels)

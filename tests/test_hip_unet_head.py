@@ -204,6 +204,26 @@ def test_seg_loss_with_logits_finer_than_the_labels(N, H, K):
 # ------------------------------------------------------------------------------------------------ the whole head
 import unet_ref as R                      # noqa: E402
 from mtp_amd import UNetHead              # noqa: E402
+from mtp_amd.engine_decode import DecodeEngine      # noqa: E402
+
+# (geometry, im2col chunk budget in bytes): the default (every 3x3 layer in one chunk), and at B = 2 a budget below one sample's columns, so every
+# 3x3 layer works one sample per chunk: 2 chunks, the weight gradient's first chunk written in place and the second added through `tmp`
+CHUNKED = dict(argnames="tag,budget", argvalues=[("flat", None), ("pyr", None), ("pyr", 1)], ids=["flat", "pyr", "pyr-chunked"])
+
+
+def _budget(monkeypatch, budget):
+    """lower the budget and watch the head's own 3x3 layers: -> the (samples, chunks) of every forward / backward call of one"""
+    seen = []
+    if budget is not None:
+        orig = DecodeEngine._chunks
+
+        def watched(self, N, HW, Kp):
+            chunks = orig(self, N, HW, Kp)
+            seen.append((N, len(chunks)))
+            return chunks
+        monkeypatch.setattr(DecodeEngine, "COLS_BUDGET", budget)
+        monkeypatch.setattr(DecodeEngine, "_chunks", watched)
+    return seen
 
 
 def _randomise_bn(head, seed):
@@ -264,8 +284,9 @@ def _assert_grads(h, sd, tol=1e-3):
         assert rel_err(p.grad.cpu(), sd[n].grad) < tol, n
 
 
-@pytest.mark.parametrize("tag", ["flat", "pyr"])
-def test_head_fp32_against_torch_restatement(tag):
+@pytest.mark.parametrize(**CHUNKED)
+def test_head_fp32_against_torch_restatement(tag, budget, monkeypatch):
+    seen = _budget(monkeypatch, budget)
     head, ins, lab, mask = _case(tag)
     logits_ref, loss_ref, dins_ref, sd = _reference(head, ins, lab, mask)
     h = head.cuda().train()
@@ -301,6 +322,7 @@ def test_head_fp32_against_torch_restatement(tag):
     feat = h._forward_feature([x.cuda() for x in ins])
     sdt = {k: v.detach().double().cpu() if v.is_floating_point() else v.cpu() for k, v in h.state_dict().items()}
     assert rel_err(feat.detach().cpu(), R.torch_unet_feature(sdt, [x.double() for x in ins], 4, True)) < 1e-3
+    assert budget is None or (len(seen) >= 16 and set(seen) == {(2, 2)}), seen      # every 3x3 layer, forward and backward: 2 chunks of one sample
 
 
 @pytest.mark.parametrize("tag", ["flat", "pyr"])
@@ -334,8 +356,9 @@ def test_head_fp32_against_reference_fixture_f19(golden, tag):
     assert rel_err(ev, torch.from_numpy(d[tag + ".logits_eval"])) < 1e-3
 
 
-@pytest.mark.parametrize("tag", ["flat", "pyr"])
-def test_loss_and_grads_fast_path_equals_autograd(tag):
+@pytest.mark.parametrize(**CHUNKED)
+def test_loss_and_grads_fast_path_equals_autograd(tag, budget, monkeypatch):
+    seen = _budget(monkeypatch, budget)
     head, ins, lab, mask = _case(tag, seed=3)
     _, loss_ref, dins_ref, sd = _reference(head, ins, lab, mask)
     h = head.cuda().train()
@@ -359,6 +382,7 @@ def test_loss_and_grads_fast_path_equals_autograd(tag):
         assert rel_err(a.grad, b) < 1e-5
     for n, p in h.named_parameters():
         assert rel_err(p.grad, fast[n]) < 1e-5, n
+    assert budget is None or (len(seen) >= 16 and set(seen) == {(2, 2)}), seen      # every 3x3 layer, forward and backward: 2 chunks of one sample
 
 
 @pytest.mark.parametrize("tag,policy", [("flat", "abs_diff"), ("pyr", "abs_diff"), ("pyr", "concat"), ("flat", "diff"), ("flat", "sum")])

@@ -12,6 +12,7 @@ import torch.nn.functional as F
 import guard
 from conftest import rel_err
 from mtp_amd import ops
+from mtp_amd.engine_decode import DecodeEngine
 import test_uper_head as TU
 from test_uper_head import randomise_bn, small_head, torch_seg_loss, torch_uper, torch_uper_feature
 
@@ -183,6 +184,24 @@ def test_seg_loss_against_torch(N, h, K, label_dtype, ignored):
 
 # ------------------------------------------------------------------------------------------------ the whole head
 GEOMS = [(16, 8, 4, 2), (20, 10, 5, 3)]
+# (geometry, im2col chunk budget in bytes): the default (every 3x3 layer in one chunk), and at B = 4 a budget below one sample's columns, so every
+# 3x3 layer works one sample per chunk: 4 chunks, the weight gradient's first chunk written in place and the others added through the reused `tmp`
+CHUNKED = dict(argnames="geom,budget", argvalues=[(GEOMS[0], None), (GEOMS[1], None), (GEOMS[0], 1)], ids=["geom0", "geom1", "geom0-chunked"])
+
+
+def _budget(monkeypatch, budget):
+    """lower the budget and watch the head's own 3x3 layers: -> the (samples, chunks) of every forward / backward call of one"""
+    seen = []
+    if budget is not None:
+        orig = DecodeEngine._chunks
+
+        def watched(self, N, HW, Kp):
+            chunks = orig(self, N, HW, Kp)
+            seen.append((N, len(chunks)))
+            return chunks
+        monkeypatch.setattr(DecodeEngine, "COLS_BUDGET", budget)
+        monkeypatch.setattr(DecodeEngine, "_chunks", watched)
+    return seen
 
 
 def _case(geom, seed=0, B=4, **kw):
@@ -217,8 +236,9 @@ def _reference(head, ins, lab, mask, dtype=torch.float64):
     return logits.detach(), loss.detach(), [x.grad for x in xi], sd
 
 
-@pytest.mark.parametrize("geom", GEOMS)
-def test_head_fp32_against_torch_restatement(geom):
+@pytest.mark.parametrize(**CHUNKED)
+def test_head_fp32_against_torch_restatement(geom, budget, monkeypatch):
+    seen = _budget(monkeypatch, budget)
     head, ins, lab, mask = _case(geom)
     logits_ref, loss_ref, dins_ref, sd = _reference(head, ins, lab, mask)
     h = head.cuda().train()
@@ -248,10 +268,26 @@ def test_head_fp32_against_torch_restatement(geom):
     # predict: logits resized to a given size
     pr = h.predict([x.cuda() for x in ins], (37, 41)).cpu()
     assert rel_err(pr, F.interpolate(ev_ref, size=(37, 41), mode="bilinear", align_corners=False)) < 1e-3
+    assert budget is None or (len(seen) >= 10 and set(seen) == {(4, 4)}), seen      # every 3x3 layer, forward and backward: 4 chunks of one sample
 
 
-@pytest.mark.parametrize("geom", GEOMS)
-def test_loss_and_grads_fast_path_equals_autograd(geom):
+def test_logit_rows_are_the_eval_forward_as_rows():
+    """logit_rows (what EncoderDecoder.encode_decode returns): the eval-mode forward laid out as rows bit for bit, columns K .. Kp zero, on the
+    first map's grid"""
+    head, ins, _, _ = _case(GEOMS[0])
+    h = head.cuda().eval()
+    with torch.no_grad():
+        ev = h([x.cuda() for x in ins])
+    r, grid = h.logit_rows([x.cuda() for x in ins])
+    N, K, H0, W0 = ev.shape
+    assert tuple(grid) == (4, 16, 16) == (N, H0, W0) and r.dtype == F32 and r.shape == (N * H0 * W0, ops.pad8(K)) and K < r.shape[1]
+    assert torch.equal(r[:, :K], ev.permute(0, 2, 3, 1).reshape(-1, K))
+    assert r[:, K:].abs().max().item() == 0
+
+
+@pytest.mark.parametrize(**CHUNKED)
+def test_loss_and_grads_fast_path_equals_autograd(geom, budget, monkeypatch):
+    seen = _budget(monkeypatch, budget)
     head, ins, lab, mask = _case(geom, seed=3)
     _, loss_ref, dins_ref, sd = _reference(head, ins, lab, mask)
     h = head.cuda().train()
@@ -262,6 +298,7 @@ def test_loss_and_grads_fast_path_equals_autograd(geom):
         assert rel_err(a.cpu(), b) < 1e-3
     for n, p in h.named_parameters():
         assert rel_err(p.grad.cpu(), sd[n].grad) < 1e-3, n
+    assert budget is None or (len(seen) >= 10 and set(seen) == {(4, 4)}), seen      # every 3x3 layer, forward and backward: 4 chunks of one sample
 
 
 def test_head_bf16_within_torch_autocast_error():
