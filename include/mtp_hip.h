@@ -608,6 +608,27 @@ int mtp_unet_up_cat_fwd(const void* x, int64_t ldx, int64_t Cx, const void* skip
 int mtp_unet_up_cat_bwd(const float* dy, int64_t lddy, float* dx, int64_t lddx, int64_t Cx, float* dskip, int64_t ldds, int64_t Cs, int64_t N, int64_t h,
                         int64_t w, int64_t hs, int64_t ws, int accumulate, mtp_stream_t stream);
 
+/* ---- scene classification head (csrc/cls_head.hip): GlobalAveragePooling + LinearClsHead + CrossEntropyLoss + Accuracy.  f32 accumulation, no float
+ * atomics: every sum has a fixed order, two calls on the same inputs give the same bits. ----
+ * pooled (N, C) f32 = mean over HW of x (N, C, HW) contiguous f32 / bf16 (any HW >= 1, rows need only element alignment); the backward overwrites
+ * dx (N, C, HW) f32 / bf16 (16-byte aligned) with dpooled[n, c] / HW */
+int mtp_gap_fwd(const void* x, int dtype, float* pooled, int64_t N, int64_t C, int64_t HW, mtp_stream_t stream);
+int mtp_gap_bwd(const float* dpooled, void* dx, int dtype, int64_t N, int64_t C, int64_t HW, mtp_stream_t stream);
+/* One launch: logits (N, K) = pooled (N, C) . w (K, C)^T + b; prob = softmax (max subtracted); pred (N) int64 = arg-max, the lowest index among
+ * ties; loss_rows (N) = logsumexp - logit[label]; loss (1) = loss_weight * mean(loss_rows), summed in sample order; dlogits (N, K) = loss_weight *
+ * (prob - onehot) / N.  Every output but logits may be NULL; labels (N) int64 in [0, K) (mtp_amd.ops checks), NULL in evaluation (then loss_rows,
+ * loss and dlogits must be NULL too).  loss needs loss_rows and `counter`: one uint32 that is 0 on entry and 0 again when the kernel has finished
+ * (the arrival count of the workgroups; calls that may overlap on different streams need a counter each). */
+int mtp_cls_ce(const float* pooled, const float* w, const float* b, const int64_t* labels, float loss_weight, float* logits, float* prob,
+               int64_t* pred, float* loss_rows, float* loss, float* dlogits, uint32_t* counter, int64_t N, int64_t C, int64_t K, mtp_stream_t stream);
+/* dw (K, C) = / += dlogits^T . pooled, db (K) = / += column sums of dlogits (accumulate), dpooled (N, C) = dlogits . w (overwritten; or NULL) */
+int mtp_cls_head_bwd(const float* dlogits, const float* pooled, const float* w, float* dw, float* db, float* dpooled, int64_t N, int64_t C, int64_t K,
+                     int accumulate, mtp_stream_t stream);
+/* Accuracy: counters (nk + 1) int64 += (hits for topk[0], ..., hits for topk[nk - 1], N).  topk: nk <= 8 ascending HOST ints in [1, K].  Rank of the
+ * label = #{j : s_j > s_label} + #{j < label : s_j == s_label}; a hit for k iff rank < k and (use_thr: s_label > thr).  Integer atomics: exact. */
+int mtp_cls_hits(const float* scores, const int64_t* labels, int64_t N, int64_t K, const int32_t* topk, int nk, float thr, int use_thr,
+                 int64_t* counters, mtp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

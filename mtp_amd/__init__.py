@@ -48,8 +48,10 @@ from .backbone import (InternImage, internimage_xl, RVSA_MTP, RVSA_MTP_branches,
                        window_partition, window_reverse)
 from .registry import BACKBONES, MODELS, build_backbone  # noqa: F401
 from .decode_heads import UNetHead, UPerHead  # noqa: F401
-from .necks import FeatureFusionNeck  # noqa: F401
+from .necks import FeatureFusionNeck, GlobalAveragePooling  # noqa: F401
+from .cls_heads import LinearClsHead  # noqa: F401
+from .classifiers import ImageClassifier  # noqa: F401
 from .segmentors import EncoderDecoder, SiamEncoderDecoder  # noqa: F401
-from .evaluation import IoUMetric  # noqa: F401
+from .evaluation import Accuracy, IoUMetric  # noqa: F401
 
 __version__ = "0.6.0"      # = mtp_version() of libmtp_hip.so ("mtp_hip 0.6 (gfx950)"): the round of the build

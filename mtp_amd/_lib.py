@@ -179,6 +179,11 @@ SIGNATURES = {
     "mtp_fuse_pair_bwd": (i32, [p, i64, p, i32, p, i64, i64, i64, i64, i32, p]),
     "mtp_unet_up_cat_fwd": (i32, [p, i64, i64, p, i64, i64, i32, p, i32, i64, i64, i64, i64, i64, i64, p]),
     "mtp_unet_up_cat_bwd": (i32, [p, i64, p, i64, i64, p, i64, i64, i64, i64, i64, i64, i64, i32, p]),
+    "mtp_gap_fwd": (i32, [p, i32, p, i64, i64, i64, p]),
+    "mtp_gap_bwd": (i32, [p, p, i32, i64, i64, i64, p]),
+    "mtp_cls_ce": (i32, [p, p, p, p, f32, p, p, p, p, p, p, p, i64, i64, i64, p]),
+    "mtp_cls_head_bwd": (i32, [p, p, p, p, p, p, i64, i64, i64, i32, p]),
+    "mtp_cls_hits": (i32, [p, p, i64, i64, C.POINTER(C.c_int32), i32, f32, i32, p, p]),
     "mtp_version": (C.c_char_p, []),
     "mtp_stream_create_low_priority": (i32, [p]),
     "mtp_stream_create_cu_mask": (i32, [p, i32, p]),

@@ -1251,3 +1251,107 @@ def seg_areas(pred, labels, K, areas, ignore_index=255):
     check(lib().mtp_seg_areas(_p(pred), pred.element_size(), _p(labels), labels.element_size(), pred.numel(), K, int(ignore_index), _p(areas), _s()),
           "mtp_seg_areas")
     return areas
+
+
+# ------------------------------------------------------------------------------------------------ scene classification (csrc/cls_head.hip)
+CLS_MAX_TOPK = 8           # mtp_cls_hits takes its k list by value
+_CLS_OUTPUTS = ("logits", "prob", "pred", "loss_rows", "loss", "dlogits")
+_cls_counters = {}
+
+
+def _cls_counter(device):
+    """the arrival counter of mtp_cls_ce: one zeroed uint32 per (device, stream), which the kernel leaves at zero -- not from _scratch (no fill launch)"""
+    key = (device.index, _s())
+    c = _cls_counters.get(key)
+    if c is None:
+        c = _cls_counters[key] = torch.zeros(4, device=device, dtype=torch.int32)
+    return c
+
+
+def _check_labels(name, labels, N, K):
+    if labels.dtype != torch.int64 or labels.shape != (N,) or not labels.is_contiguous():
+        raise TypeError("%s: labels must be a contiguous int64 tensor of shape (%d,)" % (name, N))
+    if bool(((labels < 0) | (labels >= K)).any()):
+        raise ValueError("%s: labels outside [0, %d)" % (name, K))
+
+
+def gap_fwd(x, pooled=None):
+    """x (N, C, ...) contiguous f32 / bf16 -> pooled (N, C) f32, the mean over the trailing dimensions"""
+    assert x.dim() >= 3
+    N, Cc = x.shape[:2]
+    HW = x[0, 0].numel()
+    pooled = _scratch((N, Cc), x.device, torch.float32) if pooled is None else pooled
+    assert pooled.shape == (N, Cc)
+    check(lib().mtp_gap_fwd(_p(x), _dt(x), _f32(pooled), N, Cc, HW, _s()), "mtp_gap_fwd")
+    return pooled
+
+
+def gap_bwd(dpooled, dx):
+    """dx (N, C, ...) f32 / bf16 = dpooled (N, C) f32 / HW broadcast; every element of dx is overwritten"""
+    N, Cc = dx.shape[:2]
+    assert dpooled.shape == (N, Cc)
+    check(lib().mtp_gap_bwd(_f32(dpooled), _p(dx), _dt(dx), N, Cc, dx[0, 0].numel(), _s()), "mtp_gap_bwd")
+    return dx
+
+
+def cls_ce(pooled, w, b, labels=None, loss_weight=1.0, outputs=None, check_labels=True, **bufs):
+    """pooled (N, C), w (K, C), b (K) f32 and labels (N) int64 (None: evaluation) -> dict of the requested `outputs`, one launch:
+    logits (N, K), prob (N, K) softmax, pred (N) int64 arg-max (lowest index among ties), loss_rows (N) = logsumexp - logit[label],
+    loss () = loss_weight * mean(loss_rows), dlogits (N, K) = loss_weight * (prob - onehot) / N.  Default outputs: logits, loss_rows, loss, dlogits with
+    labels; logits, prob, pred without.  A buffer handed in by name (logits=..., prob=...) is written in place.  check_labels=False skips the range check
+    (a host synchronisation) for labels that were checked before."""
+    N, Cc = pooled.shape
+    K = w.shape[0]
+    assert w.shape == (K, Cc) and b.shape == (K,)
+    if outputs is None:
+        outputs = ("logits", "loss_rows", "loss", "dlogits") if labels is not None else ("logits", "prob", "pred")
+    outputs = set(outputs) | set(bufs) | {"logits"}
+    if not outputs <= set(_CLS_OUTPUTS):
+        raise ValueError("cls_ce: unknown outputs %s" % sorted(outputs - set(_CLS_OUTPUTS)))
+    if "loss" in outputs:
+        outputs.add("loss_rows")
+    if labels is None and outputs & {"loss_rows", "loss", "dlogits"}:
+        raise ValueError("cls_ce: loss_rows / loss / dlogits need labels")
+    if labels is not None and check_labels:
+        _check_labels("cls_ce", labels, N, K)
+    shapes = {"logits": ((N, K), torch.float32), "prob": ((N, K), torch.float32), "pred": ((N,), torch.int64), "loss_rows": ((N,), torch.float32),
+              "loss": ((), torch.float32), "dlogits": ((N, K), torch.float32)}
+    out = {}
+    for name in _CLS_OUTPUTS:
+        if name in outputs:
+            t = bufs.get(name)
+            shape, dtype = shapes[name]
+            t = _scratch(shape, pooled.device, dtype) if t is None else t
+            assert t.dtype == dtype and tuple(t.shape) == shape, name
+            out[name] = t
+    ptr = [_p(out.get(name)) for name in _CLS_OUTPUTS]
+    counter = _cls_counter(pooled.device) if "loss" in out else None
+    check(lib().mtp_cls_ce(_f32(pooled), _f32(w), _f32(b), _p(labels), float(loss_weight), *ptr, _p(counter), N, Cc, K, _s()), "mtp_cls_ce")
+    return out
+
+
+def cls_head_bwd(dlogits, pooled, w, dw, db, dpooled=None, accumulate=False):
+    """dw (K, C) = / += dlogits^T . pooled, db (K) = / += column sums of dlogits, dpooled (N, C) = dlogits . w (None: not wanted); all f32, one launch"""
+    N, K = dlogits.shape
+    Cc = w.shape[1]
+    assert pooled.shape == (N, Cc) and w.shape == dw.shape == (K, Cc) and db.shape == (K,) and (dpooled is None or dpooled.shape == (N, Cc))
+    check(lib().mtp_cls_head_bwd(_f32(dlogits), _f32(pooled), _f32(w), _f32(dw), _f32(db), _f32(dpooled), N, Cc, K, int(accumulate), _s()),
+          "mtp_cls_head_bwd")
+    return dw, db, dpooled
+
+
+def cls_hits(scores, labels, topk, counters, thr=0.0):
+    """counters (len(topk) + 1) int64 += (hits for each k of topk, N).  scores (N, K) f32, labels (N) int64, topk ascending ints <= K.  The label's rank
+    = #{j : s_j > s_label} + #{j < label : s_j == s_label}; a hit for k iff rank < k and s_label > thr (thr None: no threshold)."""
+    N, K = scores.shape
+    topk = [int(k) for k in topk]
+    if not topk or len(topk) > CLS_MAX_TOPK or any(k < 1 for k in topk) or any(a >= b for a, b in zip(topk, topk[1:])):
+        raise ValueError("cls_hits: topk must be 1 to %d ascending positive ints (got %s)" % (CLS_MAX_TOPK, topk))
+    if topk[-1] > K:
+        raise ValueError("cls_hits: topk %s exceeds the %d classes" % (tuple(topk), K))
+    _check_labels("cls_hits", labels, N, K)
+    assert counters.dtype == torch.int64 and counters.shape == (len(topk) + 1,)
+    arr = (C.c_int32 * len(topk))(*topk)
+    check(lib().mtp_cls_hits(_f32(scores), _p(labels), N, K, arr, len(topk), 0.0 if thr is None else float(thr), int(thr is not None), _p(counters), _s()),
+          "mtp_cls_hits")
+    return counters
