@@ -347,12 +347,11 @@ int mtp_full_attn_bwd(const void* qkv, const void* o, const void* dout, const fl
 enum {
     MTP_ATTN_KERNEL_NONE = 0,
     MTP_FULL_FWD_V3 = 1,          /* row-aligned MFMA kernels, grids <= 16 x 16 */
-    MTP_FULL_FWD_MFMA1 = 2,       /* one workgroup per (image, head), <= 256 tokens */
+    /* value 2 of the two full-attention lists is retired (it named the deleted MFMA1 family): never returned, never reused */
     MTP_FULL_FWD_FLASH128 = 3,    /* flash, 128-key blocks (sides <= 32) */
     MTP_FULL_FWD_FLASH256 = 4,    /* flash, 256-key blocks (a side of 33 .. 64) */
     MTP_FULL_FWD_GENERIC = 5,     /* f32-math kernel */
     MTP_FULL_BWD_V3 = 1,
-    MTP_FULL_BWD_MFMA1 = 2,       /* the a / b pair, one workgroup per (image, head) */
     MTP_FULL_BWD_FLASH = 3,
     MTP_FULL_BWD_THREE_PASS = 4,  /* f32 math, > 256 tokens, needs the workspace */
     MTP_FULL_BWD_SINGLE_WG = 5,   /* f32 math, <= 256 tokens */

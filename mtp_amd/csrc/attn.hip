@@ -452,8 +452,7 @@ __global__ __launch_bounds__(256) void full_attn_bwdN_k_kernel(const T* __restri
 // RVSA forward.  grid (B*nW*heads), 64 threads (one wave): lane = key for the gather, lane = query afterwards.
 // LDS floats: Ksel[49*64] | Vsel[49*64] | relq[14*64] | sbuf[49*64] | tab[176]
 // =====================================================================================================================
-template <typename T>
-__global__ __launch_bounds__(64) void rvsa_attn_fwd_kernel(const T* __restrict__ qkv, const float* __restrict__ samp, T* __restrict__ o, float* __restrict__ lse,
+__global__ __launch_bounds__(64) void rvsa_attn_fwd_kernel(const float* __restrict__ qkv, const float* __restrict__ samp, float* __restrict__ o, float* __restrict__ lse,
                                                           const float* __restrict__ rel_h, const float* __restrict__ rel_w, const float* __restrict__ bias_table,
                                                           RvsaGeom g, float scale) {
     __shared__ __attribute__((aligned(16))) float Ksel[49 * HD];
@@ -466,7 +465,7 @@ __global__ __launch_bounds__(64) void rvsa_attn_fwd_kernel(const T* __restrict__
     const int h = blockIdx.x % H, bw = blockIdx.x / H, b = bw / nW, win = bw % nW, wi = win / g.nw, wj = win % g.nw;
     const int C = H * HD, N = g.Hp * g.Wp;
     const int64_t ld = 3 * (int64_t)C;
-    const T* base = qkv + (int64_t)b * N * ld + h * HD;
+    const float* base = qkv + (int64_t)b * N * ld + h * HD;
     const bool active = lane < 49;
     const int a = active ? lane / 7 : 0, bb = active ? lane % 7 : 0;
 
@@ -540,9 +539,8 @@ __global__ __launch_bounds__(64) void rvsa_attn_fwd_kernel(const T* __restrict__
 // RVSA backward.  grid (B*nW*heads), 64 threads.
 // LDS floats: R1[2*49*64] (Ksel|Vsel, later Q|dO) | relq[14*64] | dqr[14*64] | tab[176] | dtab[176] | lses[64] | delta[64]
 // =====================================================================================================================
-template <typename T>
-__global__ __launch_bounds__(64) void rvsa_attn_bwd_kernel(const T* __restrict__ qkv, const float* __restrict__ samp, const T* __restrict__ o, const T* __restrict__ dout,
-                                                          const float* __restrict__ lse, T* __restrict__ dqkv, float* __restrict__ dkv, float* __restrict__ dsamp,
+__global__ __launch_bounds__(64) void rvsa_attn_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ samp, const float* __restrict__ o, const float* __restrict__ dout,
+                                                          const float* __restrict__ lse, float* __restrict__ dqkv, float* __restrict__ dkv, float* __restrict__ dsamp,
                                                           float* __restrict__ rel_part, float* __restrict__ tab_part,
                                                           const float* __restrict__ rel_h, const float* __restrict__ rel_w, const float* __restrict__ bias_table,
                                                           RvsaGeom g, float scale) {
@@ -560,7 +558,7 @@ __global__ __launch_bounds__(64) void rvsa_attn_bwd_kernel(const T* __restrict__
     const int h = blockIdx.x % H, bw = blockIdx.x / H, b = bw / nW, win = bw % nW, wi = win / g.nw, wj = win % g.nw;
     const int C = H * HD, N = g.Hp * g.Wp;
     const int64_t ld = 3 * (int64_t)C;
-    const T* base = qkv + (int64_t)b * N * ld + h * HD;
+    const float* base = qkv + (int64_t)b * N * ld + h * HD;
     const bool active = lane < 49;
     const int a = active ? lane / 7 : 0, bb = active ? lane % 7 : 0;
 
@@ -771,7 +769,6 @@ size_t full_bwd1_lds(int64_t Hp, int64_t Wp) { return sizeof(float) * (size_t)(2
 int full_fwd_family(int dtype, int64_t Hp, int64_t Wp) {
     if (dtype == MTP_BF16) {
         if (mtp_full_v3_fits(Hp, Wp)) return MTP_FULL_FWD_V3;
-        if (mtp_full_mfma1_fits(Hp, Wp, false)) return MTP_FULL_FWD_MFMA1;
         const int keys = mtp_full_fwd_flash_keys(Hp, Wp);
         if (keys) return keys == 256 ? MTP_FULL_FWD_FLASH256 : MTP_FULL_FWD_FLASH128;
     }   // larger token grids fall through to the generic kernel
@@ -781,7 +778,6 @@ int full_fwd_family(int dtype, int64_t Hp, int64_t Wp) {
 int full_bwd_family(int dtype, int64_t Hp, int64_t Wp) {
     if (dtype == MTP_BF16) {
         if (mtp_full_v3_fits(Hp, Wp)) return MTP_FULL_BWD_V3;
-        if (mtp_full_mfma1_fits(Hp, Wp, true)) return MTP_FULL_BWD_MFMA1;
         if (mtp_full_bwd_flash_fits(Hp, Wp)) return MTP_FULL_BWD_FLASH;
     }
     if (Hp * Wp > 256)   // multi-workgroup three-pass backward (448^2 / 512^2 inputs); needs the caller's workspace
@@ -790,6 +786,7 @@ int full_bwd_family(int dtype, int64_t Hp, int64_t Wp) {
     return full_bwd1_lds(Hp, Wp) <= 160 * 1024 ? MTP_FULL_BWD_SINGLE_WG : MTP_ATTN_KERNEL_NONE;
 }
 
+// the generic RVSA kernels of this file are the f32 path only: every bf16 call goes to an MFMA family
 int rvsa_fwd_family(int dtype) { return dtype == MTP_BF16 ? MTP_RVSA_FWD_MFMA : MTP_RVSA_FWD_GENERIC; }
 
 int rvsa_bwd_family(int dtype, int64_t Hp, int64_t Wp, int64_t heads) {
@@ -815,8 +812,8 @@ extern "C" int mtp_full_attn_fwd(const void* qkv, void* o, float* lse, int dtype
     if (hd != HD) return MTP_ERR_UNSUPPORTED;
     switch (full_fwd_family(dtype, Hp, Wp)) {
         case MTP_FULL_FWD_V3: return mtp_full_v3_fwd_launch(qkv, o, lse, rel_h, rel_w, B, Hp, Wp, heads, scale, (hipStream_t)stream);
-        case MTP_FULL_FWD_MFMA1: case MTP_FULL_FWD_FLASH128: case MTP_FULL_FWD_FLASH256:
-            return mtp_full_fwd_mfma_launch(qkv, o, lse, rel_h, rel_w, B, Hp, Wp, heads, scale, (hipStream_t)stream);
+        case MTP_FULL_FWD_FLASH128: case MTP_FULL_FWD_FLASH256:
+            return mtp_full_fwd_flash_launch(qkv, o, lse, rel_h, rel_w, B, Hp, Wp, heads, scale, (hipStream_t)stream);
         case MTP_FULL_FWD_GENERIC: break;
         default: return MTP_ERR_UNSUPPORTED;
     }
@@ -847,7 +844,6 @@ extern "C" int mtp_full_attn_bwd(const void* qkv, const void* o, const void* dou
     const int family = full_bwd_family(dtype, Hp, Wp);
     switch (family) {
         case MTP_FULL_BWD_V3: return mtp_full_v3_bwd_launch(qkv, o, dout, lse, dqkv, rel_h, rel_w, drel_part, B, Hp, Wp, heads, scale, (hipStream_t)stream);
-        case MTP_FULL_BWD_MFMA1: return mtp_full_bwd_mfma_launch(qkv, o, dout, lse, dqkv, rel_h, rel_w, drel_part, B, Hp, Wp, heads, scale, (hipStream_t)stream);
         case MTP_FULL_BWD_FLASH:
             return mtp_full_bwd_flash_launch(qkv, o, dout, lse, dqkv, rel_h, rel_w, drel_part, workspace, B, Hp, Wp, heads, scale, (hipStream_t)stream);
         case MTP_FULL_BWD_THREE_PASS: case MTP_FULL_BWD_SINGLE_WG: break;
@@ -903,10 +899,7 @@ extern "C" int mtp_rvsa_attn_fwd(const void* qkv, const float* samp, void* o, fl
     hipStream_t s = (hipStream_t)stream;
     if (rvsa_fwd_family(dtype) == MTP_RVSA_FWD_MFMA)
         return mtp_rvsa_fwd_mfma_launch(qkv, samp, o, lse, rel_h, rel_w, bias_table, B, Hp, Wp, heads, scale, s);
-    if (dtype == MTP_BF16)
-        hipLaunchKernelGGL((rvsa_attn_fwd_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)qkv, samp, (bf16_t*)o, lse, rel_h, rel_w, bias_table, g, scale);
-    else
-        hipLaunchKernelGGL((rvsa_attn_fwd_kernel<float>), grid, block, 0, s, (const float*)qkv, samp, (float*)o, lse, rel_h, rel_w, bias_table, g, scale);
+    hipLaunchKernelGGL(rvsa_attn_fwd_kernel, grid, block, 0, s, (const float*)qkv, samp, (float*)o, lse, rel_h, rel_w, bias_table, g, scale);
     return mtp_launch_status();
 }
 
@@ -933,12 +926,8 @@ extern "C" int mtp_rvsa_attn_bwd(const void* qkv, const float* samp, const void*
         const int rc = mtp_rvsa_bwd_mfma_launch(qkv, samp, o, dout, lse, dqkv, dkv_f32, dsamp, rel_part, tab_part, rel_h, rel_w, bias_table, B, Hp, Wp, heads, scale, s);
         if (rc) return rc;
         hipLaunchKernelGGL((dkv_convert_kernel<bf16_t>), cgrid, cblock, 0, s, dkv_f32, (bf16_t*)dqkv, Ttok, (int)C);
-    } else if (dtype == MTP_BF16) {
-        hipLaunchKernelGGL((rvsa_attn_bwd_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)qkv, samp, (const bf16_t*)o, (const bf16_t*)dout, lse, (bf16_t*)dqkv,
-                           dkv_f32, dsamp, rel_part, tab_part, rel_h, rel_w, bias_table, g, scale);
-        hipLaunchKernelGGL((dkv_convert_kernel<bf16_t>), cgrid, cblock, 0, s, dkv_f32, (bf16_t*)dqkv, Ttok, (int)C);
     } else {
-        hipLaunchKernelGGL((rvsa_attn_bwd_kernel<float>), grid, block, 0, s, (const float*)qkv, samp, (const float*)o, (const float*)dout, lse, (float*)dqkv,
+        hipLaunchKernelGGL(rvsa_attn_bwd_kernel, grid, block, 0, s, (const float*)qkv, samp, (const float*)o, (const float*)dout, lse, (float*)dqkv,
                            dkv_f32, dsamp, rel_part, tab_part, rel_h, rel_w, bias_table, g, scale);
         hipLaunchKernelGGL((dkv_convert_kernel<float>), cgrid, cblock, 0, s, dkv_f32, (float*)dqkv, Ttok, (int)C);
     }

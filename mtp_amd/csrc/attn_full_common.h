@@ -1,5 +1,5 @@
-// helpers shared by the full-attention MFMA kernels (attn_full_mfma.hip: <= 256 tokens and the flash forward;
-// attn_full_flash_bwd.hip: the flash backward beyond 256 tokens).  Internal linkage: every translation unit gets its own copy.
+// helpers shared by the full-attention MFMA kernels (attn_full_v3.hip: token grids of at most 16 x 16; attn_full_flash_fwd.hip /
+// attn_full_flash_bwd.hip: the flash forward and backward beyond 256 tokens).  Internal linkage: every translation unit gets its own copy.
 #pragma once
 #include "attn_common.h"
 
@@ -23,18 +23,6 @@ __device__ __forceinline__ uint4 table_frag_t(const float* __restrict__ tab, int
     for (int e = 0; e < 8; ++e) v[e] = (r0 + e) < rows ? tab[(r0 + e) * HD + d] : 0.f;
     return pack_bf16x8(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
 }
-
-struct FGeom {
-    int N, Hp, Wp, heads, NT, NP, NP2, KK, TPV, RH, RW;
-};
-
-// K (or any 64-wide row block of qkv) -> swizzled row-major LDS image, rows >= N zeroed, up to `rows` rows
-__device__ __forceinline__ void stage_rows_swz(const bf16_t* __restrict__ src, int64_t ld, int N, int rows, char* img, int tid, int nthreads = 256) {
-    for (int idx = tid; idx < rows * 8; idx += nthreads) {
-        const int row = idx >> 3, c = idx & 7;
-        *reinterpret_cast<uint4*>(img + swz(row, c)) = row_frag(src, ld, row, row < N, 8 * c);
-    }
-}
 // K^T fragment (MFMA A operand: row d = 16 dt + fr, k = keys key0 .. key0+3 and key0+16 .. key0+19) out of the swizzled row-major K image:
 // in each 16-lane group, lane i supplies the address of row i >> 2, columns 4 (i & 3) .. +3 of a [4 keys][16 d] block and receives
 // column i of its four rows
@@ -49,7 +37,7 @@ __device__ __forceinline__ uint4 kt_frag_tr(const char* Ks, int key0, int dt, in
     return make_uint4(l.x, l.y, h.x, h.y);
 }
 
-// the same in two steps, for a software-pipelined block loop: the global loads of the NEXT block are issued into registers right behind the barrier that
+// ROWS 64-wide rows of qkv (K, V, ...) -> swizzled row-major LDS image, rows >= N zeroed, in two steps for a software-pipelined block loop: the global loads of the NEXT block are issued into registers right behind the barrier that
 // publishes the current one (prefetch_rows) and written to LDS at the top of the next trip (commit_rows) -- their latency runs under the block's MFMAs
 template <int ROWS>
 __device__ __forceinline__ void prefetch_rows(const bf16_t* __restrict__ src, int64_t ld, int N, int tid, uint4 (&r)[ROWS * 8 / 256]) {
@@ -65,19 +53,6 @@ __device__ __forceinline__ void commit_rows(char* img, int tid, const uint4 (&r)
     for (int i = 0; i < ROWS * 8 / 256; ++i) {
         const int idx = tid + 256 * i, row = idx >> 3, c = idx & 7;
         *reinterpret_cast<uint4*>(img + swz(row, c)) = r[i];
-    }
-}
-// 64-wide rows -> transposed image img[d][row] (pitch TPV bytes), columns >= N zeroed, up to `cols` columns
-__device__ __forceinline__ void stage_rows_t(const bf16_t* __restrict__ src, int64_t ld, int N, int cols, int TPV, char* img, int tid, int nthreads = 256) {
-    for (int idx = tid; idx < cols * 8; idx += nthreads) {
-        const int row = idx >> 3, c = idx & 7;
-        const uint4 v = row_frag(src, ld, row, row < N, 8 * c);
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            *reinterpret_cast<uint16_t*>(img + (8 * c + 2 * e) * TPV + row * 2) = (uint16_t)(w[e] & 0xffffu);
-            *reinterpret_cast<uint16_t*>(img + (8 * c + 2 * e + 1) * TPV + row * 2) = (uint16_t)(w[e] >> 16);
-        }
     }
 }
 

@@ -9,7 +9,7 @@
 //          delta[n] = dO_n . O_n
 //   dq   : workgroup = 64 queries, loop over blocks of 128 keys: S^T = K.Q^T, dP^T = V.dO^T, dS = P (dP - delta),
 //          dQ^T += K^T.dS^T; the gradient of the bias rows is a segmented sum of dS over the keys of one grid row / column,
-//          done on the matrix cores against 0/1 indicator operands (as in attn_full_mfma.hip); at the end
+//          done on the matrix cores against 0/1 indicator operands (as in the backward of attn_full_v3.hip); at the end
 //          dQ^T += Rh^T.dQRh + Rw^T.dQRw and the table gradients d(rel_pos_h/w) += dQR . Q (atomics into the per-(image, head) partials)
 //   dkv  : workgroup = 64 keys, loop over blocks of 64 queries: dV^T += dO^T.P, dK^T += Q^T.dS; the bias comes from the
 //          workspace rows (only the <= 8 grid rows the workgroup's keys touch, and all Wp columns)

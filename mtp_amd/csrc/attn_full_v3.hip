@@ -1,8 +1,7 @@
 // Full (global) attention of the MTP backbone on token grids of at most 16 x 16 (the 224^2 configurations: 14 x 14 = 196 tokens) --
-// Attention.forward VIT:90-111 with calc_rel_pos_spatial VIT:142-193 -- forward and backward, bf16 MFMA, gfx950.  Round 3 rewrite of
-// the <= 256-token kernels of attn_full_mfma.hip, which spent their time on three LDS look-ups per (query, key) element (two table
-// terms + the key's grid position), on fragments re-read from global memory inside the inner loops and on 16-token tiles that
-// straddle image rows.  What is different here:
+// Attention.forward VIT:90-111 with calc_rel_pos_spatial VIT:142-193 -- forward and backward, bf16 MFMA, gfx950.  The flash
+// kernels (attn_full_flash_fwd.hip) pay three LDS look-ups per (query, key) element (two table terms + the key's grid position) and work
+// on 16-token tiles that straddle image rows.  What is different here:
 //
 //  * ROW-ALIGNED TILES.  Tokens are laid out with a row pitch of 16: padded index 16 y + x (x < Wp valid, the rest zero rows), so an
 //    MFMA tile of 16 tokens is exactly one image row: tile index = y, lane-in-tile = x.
@@ -19,7 +18,7 @@
 //  * Every operand fragment comes from LDS images staged once per (image, head): K, V row-major XOR-swizzled (V^T / K^T / Q^T / dO^T
 //    fragments through ds_read_b64_tr_b16); nothing is re-read from global memory inside a tile loop.
 //
-// Orientation tricks are the ones of attn_full_mfma.hip: S^T = K.Q^T so that a query's softmax is in-lane + two shuffles and P^T is
+// Orientation tricks are the ones of attn_full_flash_fwd.hip: S^T = K.Q^T so that a query's softmax is in-lane + two shuffles and P^T is
 // directly the B operand of O^T = V^T.P^T; the backward uses both orientations (kernel A: lane = query, dQ and the table gradients;
 // kernel B: lane = key, dK and dV).  Scale convention: logits = scale * S (VIT:100 scales q before both products).
 #include "attn_launch.h"

@@ -679,8 +679,9 @@ def full_attn_bwd(qkv, o, dout, lse, dqkv, rel_h, rel_w, drel_h, drel_w, B, Hp, 
 
 
 # kernel families, as include/mtp_hip.h names them (0 = none: the entry point would refuse the grid as unsupported)
-FULL_FWD = {"v3": 1, "mfma1": 2, "flash128": 3, "flash256": 4, "generic": 5}
-FULL_BWD = {"v3": 1, "mfma1": 2, "flash": 3, "three_pass": 4, "single_wg": 5}
+# value 2 of the two full-attention tables is retired (it named the deleted "mfma1" family): never returned, never reused
+FULL_FWD = {"v3": 1, "flash128": 3, "flash256": 4, "generic": 5}
+FULL_BWD = {"v3": 1, "flash": 3, "three_pass": 4, "single_wg": 5}
 RVSA_FWD = {"generic": 1, "mfma": 2}
 RVSA_BWD = {"generic": 1, "mfma_dense": 2, "mfma_atomic": 3}
 

@@ -75,6 +75,19 @@ def test_conv_and_dcnv3_kernel_queries_mirror_the_header():
     assert lib.mtp_conv_kernel(_lib.CONV_OP_DWCONV3X3_FWD, 16, 2, 0, 0, 0, 0, 16, 2, 16, None, 1, 1, 8, 4, 1, 0) == _lib.CONV_KERNEL_NONE      # f64: unsupported
 
 
+def test_attention_family_tables_mirror_the_header():
+    """the anonymous enum of attention kernel families (mtp_full_attn_kernel / mtp_rvsa_attn_kernel) against the name tables of ops: names and values"""
+    from mtp_amd import ops
+    src = open(os.path.join(ROOT, "include", "mtp_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    body = re.search(r"enum \{([^}]*MTP_ATTN_KERNEL_NONE[^}]*)\};", src).group(1)
+    items = re.findall(r"MTP_([A-Z0-9_]+)\s*=\s*(\d+)\s*(?:,|$)", body)
+    assert len(items) == 14 == body.count("=") and items[0] == ("ATTN_KERNEL_NONE", "0")
+    for table in ("FULL_FWD", "FULL_BWD", "RVSA_FWD", "RVSA_BWD"):
+        assert getattr(ops, table) == {n[len(table) + 1:].lower(): int(v) for n, v in items if n.startswith(table + "_")}, table
+    assert sorted(n for n, _ in items[1:]) == sorted("%s_%s" % (t, k.upper()) for t in ("FULL_FWD", "FULL_BWD", "RVSA_FWD", "RVSA_BWD") for k in getattr(ops, t))
+
+
 def test_gemm_args_struct_layout():
     import ctypes as C
     from mtp_amd._lib import GemmArgs

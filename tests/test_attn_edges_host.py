@@ -208,7 +208,7 @@ def test_rvsa_case_is_what_the_gpu_test_assumes(case):
 
 def test_dispatch_queries_name_the_families_the_gpu_tests_assert():
     """the library loads without a device (as in test_abi.py): both queries swept over every grid; each family the GPU file asserts is returned for the
-    grid it names; families that no grid reaches are printed"""
+    grid it names, and every family the tables name is reached by some grid of the sweep"""
     from mtp_amd import ops
     ops.lib()
     for dt, Hp, Wp, _, _, _, ff, fb in FULL:
@@ -230,7 +230,5 @@ def test_dispatch_queries_name_the_families_the_gpu_tests_assert():
         names = getattr(ops, table)
         unreached = sorted(n for n, v in names.items() if v not in seen[table])
         print("%s: no grid of 1..64 x 1..64 reaches %s" % (table, unreached or "nothing"))
+        assert unreached == [], "%s names families that no grid can run: %s" % (table, unreached)
         assert seen[table] - {0} <= tested[table], "a reachable family has no case in test_hip_attn_edges.py: %s" % (seen[table] - {0} - tested[table])
-    # the single-workgroup MFMA kernels (full_fwd_mfma_kernel, full_bwd_a/b_mfma_kernel) take grids of <= 256 tokens with tables of <= 32 rows, i.e.
-    # sides <= 16 -- all of which the row-aligned v3 kernels take first
-    assert ops.FULL_FWD["mfma1"] not in seen["FULL_FWD"] and ops.FULL_BWD["mfma1"] not in seen["FULL_BWD"]
