@@ -628,6 +628,33 @@ int mtp_cls_head_bwd(const float* dlogits, const float* pooled, const float* w, 
 int mtp_cls_hits(const float* scores, const int64_t* labels, int64_t N, int64_t K, const int32_t* topk, int nk, float thr, int use_thr,
                  int64_t* counters, mtp_stream_t stream);
 
+/* ---- box operators of the detection families (csrc/box_ops.hip): IoU, NMS and the MaxIoU assignment.  Boxes f32, indices and labels int64; no float
+ * atomics, two calls on the same inputs give the same bits. ---- */
+typedef enum { MTP_BOX_ALIGNED = 0 /* x1, y1, x2, y2 */, MTP_BOX_ROTATED = 1 /* cx, cy, w, h, theta (radians) */ } mtp_box_kind;
+typedef enum {
+    MTP_ASSIGN_BOX = 0,       /* gts (K, 4), priors (N, 4) */
+    MTP_ASSIGN_RBOX2HBOX = 1, /* gts (K, 5) rotated, replaced by their circumscribed boxes; priors (N, 4) */
+    MTP_ASSIGN_ROTATED = 2    /* gts (K, 5), priors (N, 5) */
+} mtp_assign_calculator;
+/* out (M, N), or (M) when aligned (then M == N): IoU, or IoF (intersection / area of the boxes1 box) when iof.  Aligned boxes: mmdet bbox_overlaps
+ * (no +1, union = max(a1 + a2 - inter, eps)); rotated: mmcv box_iou_rotated (0 when either area is below 1e-14; eps unused). */
+int mtp_box_iou(const float* boxes1, const float* boxes2, float* out, int64_t M, int64_t N, int kind, int iof, int aligned, float eps,
+                mtp_stream_t stream);
+/* NMS over n <= 32768 boxes ALREADY sorted by score, descending.  mask: n x ceil(n / 64) 64-bit words (mask_bytes >= that, 8-byte aligned); word
+ * [row][cb] holds bit c for column cb * 64 + c iff column > row, groups[column] == groups[row] (groups NULL: one group) and iou > iou_threshold;
+ * only the words with cb >= row / 64 are written, and only those are read by mtp_nms_scan, which walks the rows in order: keep[0 .. count[0]) =
+ * the kept positions, ascending, at most max_keep of them (keep has room for n). */
+int mtp_nms_mask(const float* boxes, const int64_t* groups, int64_t n, int kind, float iou_threshold, void* mask, int64_t mask_bytes,
+                 mtp_stream_t stream);
+int mtp_nms_scan(const void* mask, int64_t n, int64_t max_keep, int64_t* keep, int64_t* count, mtp_stream_t stream);
+/* MaxIoUAssigner.assign_wrt_overlaps without the K x N matrix.  gt_inds (N): -1, 0 where neg_iou_lo <= max < neg_iou_hi, arg-max + 1 (lowest gt index
+ * among ties) where max >= pos_iou_thr; with match_low_quality every gt i with gt_max[i] >= min_pos_iou then overwrites, the largest i winning: all
+ * priors whose overlap equals gt_max[i] (gt_max_assign_all) or the first arg-max prior.  max_overlaps (N); labels (N) = gt_labels[gt_inds - 1] on
+ * positives, else -1.  workspace: K x 8 bytes, 8-byte aligned. */
+int mtp_max_iou_assign(const float* gts, const float* priors, const int64_t* gt_labels, int64_t K, int64_t N, int calculator, float pos_iou_thr,
+                       float neg_iou_lo, float neg_iou_hi, float min_pos_iou, int match_low_quality, int gt_max_assign_all, int64_t* gt_inds,
+                       float* max_overlaps, int64_t* labels, void* workspace, int64_t workspace_bytes, mtp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,12 +46,14 @@ def hw_queue_note():
 
 from .backbone import (InternImage, internimage_xl, RVSA_MTP, RVSA_MTP_branches, RVSA_MTP_det, RVSA_MTP_taps, ViT_Win_RVSA_V3_WSZ7, vit_b_rvsa, vit_l_rvsa,  # noqa: F401
                        window_partition, window_reverse)
-from .registry import BACKBONES, MODELS, build_backbone  # noqa: F401
+from .registry import BACKBONES, MODELS, TASK_UTILS, build_backbone  # noqa: F401
 from .decode_heads import UNetHead, UPerHead  # noqa: F401
 from .necks import FeatureFusionNeck, GlobalAveragePooling  # noqa: F401
 from .cls_heads import LinearClsHead  # noqa: F401
 from .classifiers import ImageClassifier  # noqa: F401
 from .segmentors import EncoderDecoder, SiamEncoderDecoder  # noqa: F401
 from .evaluation import Accuracy, IoUMetric  # noqa: F401
+from .ops_box import batched_nms, bbox_overlaps, box_iou_rotated, nms, nms_rotated  # noqa: F401
+from .task_modules import AssignResult, BboxOverlaps2D, MTP_RD_MaxIoUAssigner, MaxIoUAssigner, RBbox2HBboxOverlaps2D, RBboxOverlaps2D  # noqa: F401
 
 __version__ = "0.6.0"      # = mtp_version() of libmtp_hip.so ("mtp_hip 0.6 (gfx950)"): the round of the build

@@ -32,6 +32,10 @@ CONV_KERNEL_NONE, CONV_KERNEL_ELEMENT, CONV_KERNEL_V8, CONV_KERNEL_P8, CONV_KERN
 DCNV3_KERNEL_NONE, DCNV3_FWD9, DCNV3_FWD_VEC8, DCNV3_FWD_SCALAR, DCNV3_F64 = 0, 1, 2, 3, 4
 DCNV3_BWD_WINDOW_R2, DCNV3_BWD_WINDOW_R3, DCNV3_BWD_3X3_OS1, DCNV3_BWD_3X3_OS2, DCNV3_BWD_SCATTER_SHFL, DCNV3_BWD_SCATTER_ATOMIC = 5, 6, 7, 8, 9, 10
 
+# enum mtp_box_kind / mtp_assign_calculator (csrc/box_ops.hip)
+BOX_ALIGNED, BOX_ROTATED = 0, 1
+ASSIGN_BOX, ASSIGN_RBOX2HBOX, ASSIGN_ROTATED = 0, 1, 2
+
 # enum mtp_fuse_policy (mtp_fuse_pair_fwd / _bwd)
 FUSE_CONCAT, FUSE_SUM, FUSE_DIFF, FUSE_ABS_DIFF = 0, 1, 2, 3
 
@@ -184,6 +188,10 @@ SIGNATURES = {
     "mtp_cls_ce": (i32, [p, p, p, p, f32, p, p, p, p, p, p, p, i64, i64, i64, p]),
     "mtp_cls_head_bwd": (i32, [p, p, p, p, p, p, i64, i64, i64, i32, p]),
     "mtp_cls_hits": (i32, [p, p, i64, i64, C.POINTER(C.c_int32), i32, f32, i32, p, p]),
+    "mtp_box_iou": (i32, [p, p, p, i64, i64, i32, i32, i32, f32, p]),
+    "mtp_nms_mask": (i32, [p, p, i64, i32, f32, p, i64, p]),
+    "mtp_nms_scan": (i32, [p, i64, i64, p, p, p]),
+    "mtp_max_iou_assign": (i32, [p, p, p, i64, i64, i32, f32, f32, f32, f32, i32, i32, p, p, p, p, i64, p]),
     "mtp_version": (C.c_char_p, []),
     "mtp_stream_create_low_priority": (i32, [p]),
     "mtp_stream_create_cu_mask": (i32, [p, i32, p]),

@@ -1356,3 +1356,79 @@ def cls_hits(scores, labels, topk, counters, thr=0.0):
     check(lib().mtp_cls_hits(_f32(scores), _p(labels), N, K, arr, len(topk), 0.0 if thr is None else float(thr), int(thr is not None), _p(counters), _s()),
           "mtp_cls_hits")
     return counters
+
+
+# ------------------------------------------------------------------------------------------------ box operators (csrc/box_ops.hip)
+NMS_MAX_BOXES = 32768      # 512 mask words per row: n x ceil(n / 64) x 8 bytes = 128 MB of workspace at the limit
+_BOX_COLS = {_lib.BOX_ALIGNED: 4, _lib.BOX_ROTATED: 5}
+ASSIGN_CALCULATOR = {"box": _lib.ASSIGN_BOX, "rbox2hbox": _lib.ASSIGN_RBOX2HBOX, "rotated": _lib.ASSIGN_ROTATED}
+_ASSIGN_COLS = {_lib.ASSIGN_BOX: (4, 4), _lib.ASSIGN_RBOX2HBOX: (5, 4), _lib.ASSIGN_ROTATED: (5, 5)}
+
+
+def _check_boxes(name, t, cols):
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != cols:
+        raise TypeError("%s: boxes must be float32 of shape (n, %d), got %s %s" % (name, cols, t.dtype, tuple(t.shape)))
+
+
+def box_iou(boxes1, boxes2, out=None, rotated=False, iof=False, aligned=False, eps=1e-6):
+    """out (M, N) f32, or (M,) when aligned = IoU (IoF when iof) of boxes1 (M, 4 | 5) with boxes2 (N, 4 | 5): x1, y1, x2, y2, or cx, cy, w, h, theta when
+    rotated.  M, N > 0."""
+    kind = _lib.BOX_ROTATED if rotated else _lib.BOX_ALIGNED
+    _check_boxes("box_iou", boxes1, _BOX_COLS[kind])
+    _check_boxes("box_iou", boxes2, _BOX_COLS[kind])
+    M, N = boxes1.shape[0], boxes2.shape[0]
+    if aligned and M != N:
+        raise ValueError("box_iou: aligned needs as many boxes1 as boxes2 (%d, %d)" % (M, N))
+    shape = (M,) if aligned else (M, N)
+    out = _scratch(shape, boxes1.device, torch.float32) if out is None else out
+    assert out.dtype == torch.float32 and tuple(out.shape) == shape
+    check(lib().mtp_box_iou(_f32(boxes1), _f32(boxes2), _f32(out), M, N, kind, int(iof), int(aligned), float(eps), _s()), "mtp_box_iou")
+    return out
+
+
+def check_nms_count(n):
+    """the one refusal of too many boxes (ops_box asks before it sorts)"""
+    if n > NMS_MAX_BOXES:
+        raise ValueError("nms: %d boxes; at most %d (the suppression mask takes n x ceil(n / 64) x 8 bytes)" % (n, NMS_MAX_BOXES))
+
+
+def nms_sorted(boxes, iou_threshold, groups=None, rotated=False, max_keep=None):
+    """greedy NMS over boxes (n, 4 | 5) f32 ALREADY sorted by score, descending; groups (n) int64 or None: a pair suppresses only within one group.
+    -> (keep (n) int64, count (1) int64) on the device: keep[:count] = the kept positions, ascending, at most max_keep.  Two launches, no sync."""
+    kind = _lib.BOX_ROTATED if rotated else _lib.BOX_ALIGNED
+    _check_boxes("nms_sorted", boxes, _BOX_COLS[kind])
+    n = boxes.shape[0]
+    check_nms_count(n)
+    if groups is not None and (groups.dtype != torch.int64 or groups.shape != (n,)):
+        raise TypeError("nms_sorted: groups must be int64 of shape (%d,)" % n)
+    words = n * ((n + 63) // 64)
+    mask = _scratch((words,), boxes.device, torch.int64)
+    keep, count = _scratch((n,), boxes.device, torch.int64), _scratch((1,), boxes.device, torch.int64)
+    check(lib().mtp_nms_mask(_f32(boxes), _p(groups), n, kind, float(iou_threshold), _p(mask), words * 8, _s()), "mtp_nms_mask")
+    check(lib().mtp_nms_scan(_p(mask), n, n if max_keep is None or max_keep <= 0 else int(max_keep), _p(keep), _p(count), _s()), "mtp_nms_scan")
+    return keep, count
+
+
+def max_iou_assign(gts, priors, gt_labels, calculator, pos_iou_thr, neg_iou_thr, min_pos_iou=0.0, match_low_quality=True, gt_max_assign_all=True,
+                   gt_inds=None, max_overlaps=None, labels=None):
+    """MaxIoUAssigner.assign_wrt_overlaps without the K x N matrix: gts (K, 4 | 5), priors (N, 4 | 5) f32, gt_labels (K) int64, calculator 'box',
+    'rbox2hbox' (rotated gts -> circumscribed boxes) or 'rotated'; neg_iou_thr a number or a (lo, hi) pair.  K, N > 0.
+    -> gt_inds (N) int64, max_overlaps (N) f32, labels (N) int64"""
+    calc = ASSIGN_CALCULATOR[calculator] if isinstance(calculator, str) else int(calculator)
+    gc, pc = _ASSIGN_COLS[calc]
+    _check_boxes("max_iou_assign", gts, gc)
+    _check_boxes("max_iou_assign", priors, pc)
+    K, N = gts.shape[0], priors.shape[0]
+    if gt_labels.dtype != torch.int64 or gt_labels.shape != (K,):
+        raise TypeError("max_iou_assign: gt_labels must be int64 of shape (%d,)" % K)
+    lo, hi = (float(neg_iou_thr[0]), float(neg_iou_thr[1])) if isinstance(neg_iou_thr, (tuple, list)) else (0.0, float(neg_iou_thr))
+    dev = priors.device
+    gt_inds = _scratch((N,), dev, torch.int64) if gt_inds is None else gt_inds
+    max_overlaps = _scratch((N,), dev, torch.float32) if max_overlaps is None else max_overlaps
+    labels = _scratch((N,), dev, torch.int64) if labels is None else labels
+    assert gt_inds.dtype == labels.dtype == torch.int64 and gt_inds.shape == labels.shape == max_overlaps.shape == (N,)
+    ws = _scratch((K,), dev, torch.int64)
+    check(lib().mtp_max_iou_assign(_f32(gts), _f32(priors), _p(gt_labels), K, N, calc, float(pos_iou_thr), lo, hi, float(min_pos_iou),
+                                   int(bool(match_low_quality)), int(bool(gt_max_assign_all)), _p(gt_inds), _f32(max_overlaps), _p(labels), _p(ws), K * 8,
+                                   _s()), "mtp_max_iou_assign")
+    return gt_inds, max_overlaps, labels

@@ -74,6 +74,7 @@ def _make(name):
 MODELS = _make("mtp_amd_models")
 BACKBONES = _make("mtp_amd_backbones")
 ROTATED_BACKBONES = BACKBONES
+TASK_UTILS = _make("mtp_amd_task_utils")      # assigners and IoU calculators (mmdet / mmrotate register theirs in a registry of this name)
 
 
 def build_backbone(cfg):
