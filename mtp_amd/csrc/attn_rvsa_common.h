@@ -33,11 +33,11 @@ struct RvsaGeom {
 };
 inline RvsaGeom make_geom(int64_t Hp, int64_t Wp, int64_t heads) {
     RvsaGeom g;
-    const int pad_h = (int)((7 - Hp % 7) % 7), pad_w = (int)((7 - Wp % 7) % 7);
+    const RvsaWindows win(Hp, Wp);
     g.Hp = (int)Hp; g.Wp = (int)Wp;
-    g.pad_t = pad_h / 2; g.pad_l = pad_w / 2;
-    g.He = (int)Hp + pad_h; g.We = (int)Wp + pad_w;
-    g.nh = g.He / 7; g.nw = g.We / 7;
+    g.pad_t = win.pad_t; g.pad_l = win.pad_l;
+    g.nh = win.nh; g.nw = win.nw;
+    g.He = 7 * g.nh; g.We = 7 * g.nw;
     g.heads = (int)heads;
     g.inv_div_x = 1.0f / (float)(Hp / 7);   // VIT:359: x offset / (h // ws)
     g.inv_div_y = 1.0f / (float)(Wp / 7);   // VIT:360: y offset / (w // ws)

@@ -207,6 +207,24 @@ static inline int mtp_optin_lds(const void* kern, int bytes, unsigned long long&
 // dispatch sizes tiles, strips and persistent grids by it (a 128-CU stream runs M / 2 rows with the tile quantisation of M rows on 256 CUs).
 int mtp_stream_cus(hipStream_t stream);
 
+// grid size of a grid-stride kernel: ceil(n / per_block) workgroups, at least 1 and at most `cap`
+static inline unsigned blocks_for(int64_t n, int per_block, int64_t cap = 1 << 20) {
+    int64_t b = (n + per_block - 1) / per_block;
+    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+
+// The 7 x 7 windows of an RVSA block over an (Hp, Wp) token map: zero padding to multiples of 7, split evenly with the odd row / column at
+// the bottom / right (VIT:229-230).  ONE definition for the attention kernels (make_geom), the sampling heads and the windowed LayerNorm
+// backward: all of them must agree on where every window lies.
+struct RvsaWindows {
+    int pad_t, pad_l, nh, nw;
+    RvsaWindows(int64_t Hp, int64_t Wp) {
+        const int pad_h = (int)((7 - Hp % 7) % 7), pad_w = (int)((7 - Wp % 7) % 7);
+        pad_t = pad_h / 2; pad_l = pad_w / 2;
+        nh = (int)((Hp + pad_h) / 7); nw = (int)((Wp + pad_w) / 7);
+    }
+};
+
 static inline int mtp_launch_status() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;

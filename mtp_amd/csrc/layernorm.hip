@@ -577,8 +577,8 @@ extern "C" int mtp_layernorm_bwd_win(const void* dy, int dy_dtype, const void* x
     if (!dy || !x || !mean || !rstd || !gamma || !dx || !dgamma_part || !dbeta_part || rows <= 0 || rows > INT32_MAX || (C % 4) || C > 256 * MAXV) return MTP_ERR_ARG;
     if (!win_add || B <= 0 || Hp <= 0 || Wp <= 0 || B * Hp * Wp != rows) return MTP_ERR_ARG;
     if (dx_copy && copy_dtype != dy_dtype) return MTP_ERR_ARG;
-    const int pad_h = (int)((7 - Hp % 7) % 7), pad_w = (int)((7 - Wp % 7) % 7);
-    const LnWin wg = {(int)Hp, (int)Wp, pad_h / 2, pad_w / 2, (int)((Hp + pad_h) / 7), (int)((Wp + pad_w) / 7)};
+    const RvsaWindows win(Hp, Wp);
+    const LnWin wg = {(int)Hp, (int)Wp, win.pad_t, win.pad_l, win.nh, win.nw};
     hipStream_t s = (hipStream_t)stream;
     if (dy_dtype == MTP_BF16 && x_dtype == MTP_F32 && dx_dtype == MTP_F32)
         return launch_ln_bwd<bf16_t, float, float>(dy, x, mean, rstd, gamma, nullptr, 0, dres, extra, dx, dx_copy, copy_scale, rows_per_sample, dgamma_part, dbeta_part, part_ld, rows, C, s, win_add, wg);

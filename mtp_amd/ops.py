@@ -517,30 +517,36 @@ def transpose_cast(src, dst):
     return dst
 
 
+def _wimg_table(rows, device):
+    """rows (src_ptr, w, wt, R, C, f32_out, wd), one per matrix -> (the mtp_wimg_desc table in device memory, total_tiles, the images to keep alive);
+    a matrix owns ceil(R / 64) * ceil(C / 64) consecutive tiles (= workgroups of the launch) from its tile0 on"""
+    arr = (_lib.WimgDesc * len(rows))()
+    tile0, keep = 0, []
+    for i, (ptr, w, wt, R, Cc, f32_out, wd) in enumerate(rows):
+        d = arr[i]
+        d.src, d.w, d.wt = ptr, _p(w), _p(wt)
+        d.R, d.C, d.tile0, d.f32_out, d.wd = R, Cc, tile0, int(bool(f32_out)), wd
+        tile0 += ((R + 63) // 64) * ((Cc + 63) // 64)
+        keep.append((w, wt))
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device), tile0, keep
+
+
 class WeightImages:
     """Descriptor table (in device memory) for mtp_weight_images: every GEMM-side image of the f32 master weights is
     refreshed by ONE launch per optimizer step.  entries: (src (R,C) f32, w or None, wt or None, f32_out)."""
 
     def __init__(self, entries, act_dtype):
-        n = len(entries)
-        arr = (_lib.WimgDesc * n)()
-        tile0 = 0
-        self.keep = []
-        for i, (src, w, wt, f32_out) in enumerate(entries):
+        rows = []
+        for src, w, wt, f32_out in entries:
             assert src.dim() == 2 and src.dtype == torch.float32
             R, Cc = src.shape
             want = torch.float32 if f32_out else act_dtype
             for img in (w, wt):
                 assert img is None or (img.dtype == want and img.numel() == R * Cc)
-            d = arr[i]
-            d.src, d.w, d.wt = _f32(src), _p(w), _p(wt)
-            d.R, d.C, d.tile0, d.f32_out = R, Cc, tile0, int(bool(f32_out))
-            tile0 += ((R + 63) // 64) * ((Cc + 63) // 64)
-            self.keep.append((src, w, wt))
-        self.n, self.total_tiles, self.act = n, tile0, _DT[act_dtype]
-        self.entries, self.act_dtype = list(entries), act_dtype
-        dev = entries[0][0].device
-        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+            rows.append((_f32(src), w, wt, R, Cc, f32_out, 0.0))
+        self.table, self.total_tiles, self.keep = _wimg_table(rows, entries[0][0].device)
+        self.n, self.act = len(rows), _DT[act_dtype]
+        self.entries, self.act_dtype = list(entries), act_dtype       # (the entries keep the sources alive)
 
     def refresh(self):
         check(lib().mtp_weight_images(self.table.data_ptr(), self.n, self.total_tiles, self.act, _s()), "mtp_weight_images")
@@ -585,30 +591,18 @@ class AdamWImages:
         if used != len(by_ptr):
             return None               # an image whose source is not a flat parameter
         self = AdamWImages()
-        arr = (_lib.WimgDesc * len(rows))()
-        tile0 = 0
-        self.keep = []
-        for i, (ptr, w, wt, R, Cc, f32_out, wd) in enumerate(rows):
-            d = arr[i]
-            d.src, d.w, d.wt = ptr, _p(w), _p(wt)
-            d.R, d.C, d.tile0, d.f32_out, d.wd = R, Cc, tile0, int(bool(f32_out)), wd
-            tile0 += ((R + 63) // 64) * ((Cc + 63) // 64)
-            self.keep.append((w, wt))
-        self.n, self.total_tiles = len(rows), tile0
+        self.table, self.total_tiles, self.keep = _wimg_table(rows, flat.data.device)
+        self.n = len(rows)
         self.act = _DT[wimg.act_dtype] if wimg is not None else MTP_BF16
-        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(flat.data.device)
         self.lr = None if lr_of is None else torch.tensor(scales, dtype=torch.float32).to(flat.data.device)     # (one scale per descriptor)
         self.flat = flat
         return self
 
     def step(self, m, v, hyper, sqn, max_norm, grad_scale):
         f = self.flat
-        if self.lr is not None:
-            check(lib().mtp_adamw_weight_images_lr(self.table.data_ptr(), _f32(self.lr), self.n, self.total_tiles, self.act, _f32(f.data), _f32(f.grad), _f32(m), _f32(v),
-                                                   _f32(hyper), _f32(sqn), max_norm, grad_scale, _s()), "mtp_adamw_weight_images_lr")
-            return
-        check(lib().mtp_adamw_weight_images(self.table.data_ptr(), self.n, self.total_tiles, self.act, _f32(f.data), _f32(f.grad), _f32(m), _f32(v), _f32(hyper),
-                                            _f32(sqn), max_norm, grad_scale, _s()), "mtp_adamw_weight_images")
+        fn, lr = ("mtp_adamw_weight_images", ()) if self.lr is None else ("mtp_adamw_weight_images_lr", (_f32(self.lr),))
+        check(getattr(lib(), fn)(self.table.data_ptr(), *lr, self.n, self.total_tiles, self.act, _f32(f.data), _f32(f.grad), _f32(m), _f32(v), _f32(hyper),
+                                 _f32(sqn), max_norm, grad_scale, _s()), fn)
 
 
 def convt_pack(w, wg, wgT):
@@ -703,6 +697,7 @@ def rvsa_attn_kernel(dtype, Hp, Wp, heads, backward=False):
 
 
 def rvsa_windows(Hp, Wp):
+    """(nh, nw) windows of an RVSA block: must match RvsaWindows in csrc/common.h, the one C definition (the host sizes buffers with it before any call)"""
     nh = (Hp + (7 - Hp % 7) % 7) // 7
     nw = (Wp + (7 - Wp % 7) % 7) // 7
     return nh, nw

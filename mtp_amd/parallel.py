@@ -43,7 +43,65 @@ def execution_order(names, depth):
     return used + unused, {n: group(n) for n in names}
 
 
-class FlatParams:
+class FlatLayout:
+    """What every flat f32 parameter buffer shares: `names` in buffer order, each parameter at offsets[name] (a multiple of ALIGN) with shapes[name], and
+    the per-parameter optimizer segments derived from that layout.  Subclasses decide the order, allocate data / grad and set `groups`."""
+
+    NO_DECAY_NAMES = ("pos_embed", "cls_token")
+
+    def _lay_out(self, names, params):
+        """offsets and shapes of `names` in this order, every parameter padded to ALIGN elements; returns the total length"""
+        self.names, self.offsets, self.shapes = list(names), {}, {}
+        off = 0
+        for n in self.names:
+            self.offsets[n], self.shapes[n] = off, tuple(params[n].shape)
+            off += self.padded(params[n].numel())
+        return off
+
+    @staticmethod
+    def padded(numel):
+        return (numel + ALIGN - 1) // ALIGN * ALIGN
+
+    def view(self, flat, n):
+        o = self.offsets[n]
+        numel = 1
+        for s in self.shapes[n]:
+            numel *= s
+        return flat[o:o + numel].view(self.shapes[n])
+
+    def no_decay(self, n, names=NO_DECAY_NAMES):
+        """the reference's rule (mmcv_custom/layer_decay_optimizer_constructor_vit.py:43-48): 1-D params, biases, pos_embed / cls_token -> weight decay 0"""
+        return len(self.shapes[n]) == 1 or n.endswith(".bias") or n in names
+
+    def weight_decay_segments(self, weight_decay, no_decay=NO_DECAY_NAMES):
+        """per-parameter segments (start offsets, wd) following the no_decay rule"""
+        starts = [self.offsets[n] for n in self.names]
+        wds = [0.0 if self.no_decay(n, no_decay) else weight_decay for n in self.names]
+        return torch.tensor(starts, dtype=torch.int64), torch.tensor(wds, dtype=torch.float32)
+
+    def group_segments(self, param_groups):
+        """per-parameter segments (start offsets, wd, lr scale) from [(group_name, lr_scale, weight_decay, [names])].  Every parameter that
+        receives a gradient must be in exactly one group; the others (outside the updated range) get wd 0, scale 1."""
+        of = {}
+        for g, scale, wd, names in param_groups:
+            for n in names:
+                if n in of:
+                    raise ValueError("parameter %r is in two optimizer groups (%s, %s)" % (n, of[n][0], g))
+                of[n] = (g, scale, wd)
+        missing = [n for n in self.names if self.groups[n] is not None and n not in of]
+        if missing:
+            raise ValueError("%d trained parameters are in no optimizer group (first: %r); a parameter with requires_grad=False inside the trained range "
+                             "is not supported with layer-wise lr decay" % (len(missing), missing[0]))
+        starts, wds, lrs = [], [], []
+        for n in self.names:
+            _, scale, wd = of.get(n, (None, 1.0, 0.0))
+            starts.append(self.offsets[n])
+            wds.append(wd)
+            lrs.append(scale)
+        return torch.tensor(starts, dtype=torch.int64), torch.tensor(wds, dtype=torch.float32), torch.tensor(lrs, dtype=torch.float32)
+
+
+class FlatParams(FlatLayout):
     def __init__(self, module, unused=()):
         params = dict(module.named_parameters())
         if hasattr(module, "_flat_param_order"):        # backbones with another layer structure (InternImage) supply their own grouping
@@ -54,16 +112,11 @@ class FlatParams:
         for n in unused:
             groups[n] = None
         order = [n for n in order if groups[n] is not None] + [n for n in order if groups[n] is None]
-        self.names, self.groups, self.offsets, self.shapes = order, groups, {}, {}
-        off = 0
-        for n in order:
-            self.offsets[n] = off
-            self.shapes[n] = tuple(params[n].shape)
-            off += (params[n].numel() + ALIGN - 1) // ALIGN * ALIGN
-        self.total = off
+        self.groups = groups
+        self.total = off = self._lay_out(order, params)
         used = [n for n in order if groups[n] is not None]
         last = used[-1]
-        self.reduced = self.offsets[last] + (params[last].numel() + ALIGN - 1) // ALIGN * ALIGN   # [0, reduced) is all-reduced
+        self.reduced = self.offsets[last] + self.padded(params[last].numel())   # [0, reduced) is all-reduced
         dev = next(iter(params.values())).device
         self.data = torch.zeros(off, device=dev, dtype=torch.float32)
         self.grad = torch.zeros(off, device=dev, dtype=torch.float32)
@@ -103,19 +156,11 @@ class FlatParams:
             from . import ops
             ops.zero_segments(self.grad, *self._zero_tab)
 
-    def view(self, flat, n):
-        o = self.offsets[n]
-        numel = 1
-        for s in self.shapes[n]:
-            numel *= s
-        return flat[o:o + numel].view(self.shapes[n])
-
     def group_end(self, gid):
         """end offset (exclusive, aligned) of the last parameter of group gid."""
         ns = [n for n in self.names if self.groups[n] == gid]
         n = ns[-1]
-        numel = self.view(self.data, n).numel()
-        return self.offsets[n] + (numel + ALIGN - 1) // ALIGN * ALIGN
+        return self.offsets[n] + self.padded(self.view(self.data, n).numel())
 
     def buckets(self, bucket_bytes=256 << 20):
         """[(last_group_id, start, end)] in completion order; a bucket closes when it reaches bucket_bytes."""
@@ -129,50 +174,14 @@ class FlatParams:
                 start = end
         return out
 
-    def weight_decay_segments(self, weight_decay, no_decay=("pos_embed", "cls_token")):
-        """per-parameter segments (start offsets, wd) following the reference's rule: 1-D params, biases, pos_embed -> 0."""
-        starts, wds = [], []
-        for n in self.names:
-            nd = len(self.shapes[n]) == 1 or n.endswith(".bias") or n in no_decay
-            starts.append(self.offsets[n])
-            wds.append(0.0 if nd else weight_decay)
-        return torch.tensor(starts, dtype=torch.int64), torch.tensor(wds, dtype=torch.float32)
 
-    def group_segments(self, param_groups):
-        """per-parameter segments (start offsets, wd, lr scale) from [(group_name, lr_scale, weight_decay, [names])].  Every parameter that
-        receives a gradient must be in exactly one group; the others (outside the updated range) get wd 0, scale 1."""
-        of = {}
-        for g, scale, wd, names in param_groups:
-            for n in names:
-                if n in of:
-                    raise ValueError("parameter %r is in two optimizer groups (%s, %s)" % (n, of[n][0], g))
-                of[n] = (g, scale, wd)
-        missing = [n for n in self.names if self.groups[n] is not None and n not in of]
-        if missing:
-            raise ValueError("%d trained parameters are in no optimizer group (first: %r); a parameter with requires_grad=False inside the trained range "
-                             "is not supported with layer-wise lr decay" % (len(missing), missing[0]))
-        starts, wds, lrs = [], [], []
-        for n in self.names:
-            _, scale, wd = of.get(n, (None, 1.0, 0.0))
-            starts.append(self.offsets[n])
-            wds.append(wd)
-            lrs.append(scale)
-        return torch.tensor(starts, dtype=torch.int64), torch.tensor(wds, dtype=torch.float32), torch.tensor(lrs, dtype=torch.float32)
-
-
-class HeadFlat:
+class HeadFlat(FlatLayout):
     """a decode head's trained parameters in one flat f32 buffer of their own (data + gradient), the parameters and their .grad re-pointed at views
     of it as FlatParams does for the backbone: the head's gradients are exchanged, clipped and stepped as one more flat range."""
 
     def __init__(self, head, names):
         params = dict(head.named_parameters())
-        self.names = list(names)
-        self.offsets, self.shapes = {}, {}
-        off = 0
-        for n in self.names:
-            self.offsets[n], self.shapes[n] = off, tuple(params[n].shape)
-            off += (params[n].numel() + ALIGN - 1) // ALIGN * ALIGN
-        self.total = self.reduced = off
+        self.total = self.reduced = off = self._lay_out(names, params)
         dev = params[self.names[0]].device
         self.data = torch.zeros(off, device=dev, dtype=torch.float32)
         self.grad = torch.zeros(off, device=dev, dtype=torch.float32)
@@ -184,10 +193,6 @@ class HeadFlat:
                 params[n].data = v
                 params[n].grad = self.view(self.grad, n)
         self.G = {n: self.view(self.grad, n) for n in self.names}
-
-    view = FlatParams.view
-    weight_decay_segments = FlatParams.weight_decay_segments
-    group_segments = FlatParams.group_segments
 
 
 def head_param_groups(names, shapes, weight_decay):
@@ -428,7 +433,7 @@ class FlatAdamW:
     def __init__(self, flat, lr=6e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05, max_norm=5.0, total_steps=None, world_size=1, param_groups=None):
         """param_groups: [(group_name, lr_scale, weight_decay, [names])] (mtp_amd.optim_groups.layer_decay_param_groups) -- every trained parameter
         takes its group's lr scale and weight decay (torch.optim.AdamW with per-group lr; the *_lr kernels).  None: reference_param_groups' two
-        groups, lr_scale 1 and the no-decay rule of FlatParams.weight_decay_segments."""
+        groups, lr_scale 1 and the no-decay rule of FlatLayout.no_decay."""
         self.flat, self.lr0, self.betas, self.eps, self.max_norm = flat, lr, betas, eps, max_norm
         self.weight_decay = weight_decay
         self.total_steps, self.world = total_steps, world_size
@@ -557,13 +562,11 @@ class FlatAdamW:
         self._fused, self._fused_for = None, wimg
         if wimg is None or not self.flat.data.is_cuda or os.environ.get("MTP_FUSED_ADAMW", "1") == "0":
             return False
-        if self.param_groups is not None:        # layer-wise lr decay: the group's weight decay and lr scale (= FlatParams.group_segments)
+        if self.param_groups is not None:        # layer-wise lr decay: the group's weight decay and lr scale (= FlatLayout.group_segments)
             of = {n: (s, w) for _, s, w, ns in self.param_groups for n in ns}
             self._fused = ops.AdamWImages.build(self.flat, wimg, lambda n: of[n][1], lr_of=lambda n: of[n][0])
             return self._fused is not None
-        no_decay = ("pos_embed", "cls_token")
-        wd = lambda n: 0.0 if (len(self.flat.shapes[n]) == 1 or n.endswith(".bias") or n in no_decay) else self.weight_decay      # (= FlatParams.weight_decay_segments)
-        self._fused = ops.AdamWImages.build(self.flat, wimg, wd)
+        self._fused = ops.AdamWImages.build(self.flat, wimg, lambda n: 0.0 if self.flat.no_decay(n) else self.weight_decay)
         return self._fused is not None
 
     def _rest_table(self, covered):
