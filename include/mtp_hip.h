@@ -14,6 +14,8 @@
  *   - inputs must be contiguous (leading dimensions are passed where a kernel supports strides) and 16-byte
  *     aligned; token tensors are row-major (T, C) with T = B*Hp*Wp (row t = (b, y, x));
  *   - return value: 0 = launched; MTP_ERR_* (<0) = argument check failed (nothing launched); >0 = hipError_t;
+ *   - a dtype the entry point has no kernel for (anything but MTP_F32 / MTP_BF16, and MTP_F64 outside DCNv3) is such a
+ *     failure: MTP_ERR_UNSUPPORTED, or MTP_ERR_ARG where the dtype is part of the argument check -- never a launch;
  *   - dtype arguments use mtp_dtype; "ACT" tensors are bf16 (throughput mode) or f32 (parity mode); statistics,
  *     parameters, parameter gradients and the residual stream are always f32.
  */

@@ -797,12 +797,12 @@ int rvsa_bwd_family(int dtype, int64_t Hp, int64_t Wp, int64_t heads) {
 }  // namespace
 
 extern "C" int mtp_full_attn_kernel(int dtype, int64_t Hp, int64_t Wp, int backward) {
-    if ((dtype != MTP_F32 && dtype != MTP_BF16) || Hp <= 0 || Wp <= 0) return MTP_ERR_ARG;
+    if (!dt_ok(dtype) || Hp <= 0 || Wp <= 0) return MTP_ERR_ARG;
     return backward ? full_bwd_family(dtype, Hp, Wp) : full_fwd_family(dtype, Hp, Wp);
 }
 
 extern "C" int mtp_rvsa_attn_kernel(int dtype, int64_t Hp, int64_t Wp, int64_t heads, int backward) {
-    if ((dtype != MTP_F32 && dtype != MTP_BF16) || Hp < 7 || Wp < 7 || heads <= 0) return MTP_ERR_ARG;
+    if (!dt_ok(dtype) || Hp < 7 || Wp < 7 || heads <= 0) return MTP_ERR_ARG;
     return backward ? rvsa_bwd_family(dtype, Hp, Wp, heads) : rvsa_fwd_family(dtype);
 }
 
@@ -821,14 +821,11 @@ extern "C" int mtp_full_attn_fwd(const void* qkv, void* o, float* lse, int dtype
     const size_t lds = full_fwd_generic_lds(Hp, Wp);
     dim3 grid((unsigned)(B * heads), (unsigned)((N + 255) / 256)), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == MTP_BF16) {
-        (void)hipFuncSetAttribute((const void*)full_attn_fwd_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((full_attn_fwd_kernel<bf16_t>), grid, block, lds, s, (const bf16_t*)qkv, (bf16_t*)o, lse, rel_h, rel_w, N, (int)Hp, (int)Wp, (int)heads, scale);
-    } else {
-        (void)hipFuncSetAttribute((const void*)full_attn_fwd_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((full_attn_fwd_kernel<float>), grid, block, lds, s, (const float*)qkv, (float*)o, lse, rel_h, rel_w, N, (int)Hp, (int)Wp, (int)heads, scale);
-    }
-    return mtp_launch_status();
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        (void)hipFuncSetAttribute((const void*)full_attn_fwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        full_attn_fwd_kernel<T><<<grid, block, lds, s>>>((const T*)qkv, (T*)o, lse, rel_h, rel_w, N, (int)Hp, (int)Wp, (int)heads, scale);
+    });
 }
 
 extern "C" int64_t mtp_full_attn_bwd_workspace_floats(int64_t B, int64_t Hp, int64_t Wp, int64_t heads) {
@@ -857,49 +854,35 @@ extern "C" int mtp_full_attn_bwd(const void* qkv, const void* o, const void* dou
         const size_t lds_k = sizeof(float) * (size_t)(2 * KT * HD + HW * KT + 2 * KT);
         hipStream_t s = (hipStream_t)stream;
         dim3 gq((unsigned)(B * heads), (unsigned)((N + 255) / 256)), gt((unsigned)(B * heads), (unsigned)((RT + 3) / 4)), block(256);
-        if (dtype == MTP_BF16) {
-            (void)hipFuncSetAttribute((const void*)full_attn_bwdN_q_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q);
-            hipLaunchKernelGGL((full_attn_bwdN_q_kernel<bf16_t>), gq, block, lds_q, s, (const bf16_t*)qkv, (const bf16_t*)o, (const bf16_t*)dout, lse, (bf16_t*)dqkv,
-                               rel_h, rel_w, workspace, N, (int)Hp, (int)Wp, (int)heads, scale);
-            hipLaunchKernelGGL((full_attn_bwdN_t_kernel<bf16_t>), gt, block, 0, s, (const bf16_t*)qkv, (const float*)workspace, drel_part, N, (int)Hp, (int)Wp, (int)heads, scale);
-            hipLaunchKernelGGL((full_attn_bwdN_k_kernel<bf16_t>), gq, block, lds_k, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse, (bf16_t*)dqkv,
-                               (const float*)workspace, N, (int)Hp, (int)Wp, (int)heads, scale);
-        } else {
-            (void)hipFuncSetAttribute((const void*)full_attn_bwdN_q_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q);
-            hipLaunchKernelGGL((full_attn_bwdN_q_kernel<float>), gq, block, lds_q, s, (const float*)qkv, (const float*)o, (const float*)dout, lse, (float*)dqkv,
-                               rel_h, rel_w, workspace, N, (int)Hp, (int)Wp, (int)heads, scale);
-            hipLaunchKernelGGL((full_attn_bwdN_t_kernel<float>), gt, block, 0, s, (const float*)qkv, (const float*)workspace, drel_part, N, (int)Hp, (int)Wp, (int)heads, scale);
-            hipLaunchKernelGGL((full_attn_bwdN_k_kernel<float>), gq, block, lds_k, s, (const float*)qkv, (const float*)dout, lse, (float*)dqkv,
-                               (const float*)workspace, N, (int)Hp, (int)Wp, (int)heads, scale);
-        }
-        return mtp_launch_status();
+        return for_act(dtype, [&](auto t) {
+            using T = decltype(t);
+            (void)hipFuncSetAttribute((const void*)full_attn_bwdN_q_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q);
+            full_attn_bwdN_q_kernel<T><<<gq, block, lds_q, s>>>((const T*)qkv, (const T*)o, (const T*)dout, lse, (T*)dqkv, rel_h, rel_w, workspace, N, (int)Hp, (int)Wp, (int)heads, scale);
+            full_attn_bwdN_t_kernel<T><<<gt, block, 0, s>>>((const T*)qkv, (const float*)workspace, drel_part, N, (int)Hp, (int)Wp, (int)heads, scale);
+            full_attn_bwdN_k_kernel<T><<<gq, block, lds_k, s>>>((const T*)qkv, (const T*)dout, lse, (T*)dqkv, (const float*)workspace, N, (int)Hp, (int)Wp, (int)heads, scale);
+        });
     }
     const size_t lds = full_bwd1_lds(Hp, Wp);
     dim3 grid((unsigned)(B * heads)), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == MTP_BF16) {
-        (void)hipFuncSetAttribute((const void*)full_attn_bwd_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((full_attn_bwd_kernel<bf16_t>), grid, block, lds, s, (const bf16_t*)qkv, (const bf16_t*)o, (const bf16_t*)dout, lse, (bf16_t*)dqkv,
-                           rel_h, rel_w, drel_part, N, (int)Hp, (int)Wp, (int)heads, scale);
-    } else {
-        (void)hipFuncSetAttribute((const void*)full_attn_bwd_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((full_attn_bwd_kernel<float>), grid, block, lds, s, (const float*)qkv, (const float*)o, (const float*)dout, lse, (float*)dqkv,
-                           rel_h, rel_w, drel_part, N, (int)Hp, (int)Wp, (int)heads, scale);
-    }
-    return mtp_launch_status();
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        (void)hipFuncSetAttribute((const void*)full_attn_bwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        full_attn_bwd_kernel<T><<<grid, block, lds, s>>>((const T*)qkv, (const T*)o, (const T*)dout, lse, (T*)dqkv, rel_h, rel_w, drel_part, N, (int)Hp, (int)Wp, (int)heads, scale);
+    });
 }
 
 extern "C" int mtp_rvsa_attn_fwd(const void* qkv, const float* samp, void* o, float* lse, int dtype,
                                  const float* rel_h, const float* rel_w, const float* bias_table,
                                  int64_t B, int64_t Hp, int64_t Wp, int64_t heads, int64_t hd, float scale, mtp_stream_t stream) {
     if (!qkv || !samp || !o || !lse || !rel_h || !rel_w || !bias_table || B <= 0 || Hp < 7 || Wp < 7 || heads <= 0) return MTP_ERR_ARG;
-    if (hd != HD) return MTP_ERR_UNSUPPORTED;
+    if (hd != HD || !dt_ok(dtype)) return MTP_ERR_UNSUPPORTED;
     const RvsaGeom g = make_geom(Hp, Wp, heads);
     dim3 grid((unsigned)(B * g.nh * g.nw * heads)), block(64);
     hipStream_t s = (hipStream_t)stream;
     if (rvsa_fwd_family(dtype) == MTP_RVSA_FWD_MFMA)
         return mtp_rvsa_fwd_mfma_launch(qkv, samp, o, lse, rel_h, rel_w, bias_table, B, Hp, Wp, heads, scale, s);
-    hipLaunchKernelGGL(rvsa_attn_fwd_kernel, grid, block, 0, s, (const float*)qkv, samp, (float*)o, lse, rel_h, rel_w, bias_table, g, scale);
+    rvsa_attn_fwd_kernel<<<grid, block, 0, s>>>((const float*)qkv, samp, (float*)o, lse, rel_h, rel_w, bias_table, g, scale);
     return mtp_launch_status();
 }
 
@@ -909,7 +892,7 @@ extern "C" int mtp_rvsa_attn_bwd(const void* qkv, const float* samp, const void*
                                  int64_t B, int64_t Hp, int64_t Wp, int64_t heads, int64_t hd, float scale, mtp_stream_t stream) {
     if (!qkv || !samp || !o || !dout || !lse || !dqkv || !dkv_f32 || !dsamp || !rel_part || !tab_part || !rel_h || !rel_w || !bias_table) return MTP_ERR_ARG;
     if (B <= 0 || Hp < 7 || Wp < 7 || heads <= 0) return MTP_ERR_ARG;
-    if (hd != HD) return MTP_ERR_UNSUPPORTED;
+    if (hd != HD || !dt_ok(dtype)) return MTP_ERR_UNSUPPORTED;
     const RvsaGeom g = make_geom(Hp, Wp, heads);
     const int64_t Ttok = B * Hp * Wp, C = heads * HD;
     hipStream_t s = (hipStream_t)stream;
@@ -925,11 +908,11 @@ extern "C" int mtp_rvsa_attn_bwd(const void* qkv, const float* samp, const void*
     if (family == MTP_RVSA_BWD_MFMA_ATOMIC) {
         const int rc = mtp_rvsa_bwd_mfma_launch(qkv, samp, o, dout, lse, dqkv, dkv_f32, dsamp, rel_part, tab_part, rel_h, rel_w, bias_table, B, Hp, Wp, heads, scale, s);
         if (rc) return rc;
-        hipLaunchKernelGGL((dkv_convert_kernel<bf16_t>), cgrid, cblock, 0, s, dkv_f32, (bf16_t*)dqkv, Ttok, (int)C);
+        dkv_convert_kernel<bf16_t><<<cgrid, cblock, 0, s>>>(dkv_f32, (bf16_t*)dqkv, Ttok, (int)C);
     } else {
-        hipLaunchKernelGGL(rvsa_attn_bwd_kernel, grid, block, 0, s, (const float*)qkv, samp, (const float*)o, (const float*)dout, lse, (float*)dqkv,
+        rvsa_attn_bwd_kernel<<<grid, block, 0, s>>>((const float*)qkv, samp, (const float*)o, (const float*)dout, lse, (float*)dqkv,
                            dkv_f32, dsamp, rel_part, tab_part, rel_h, rel_w, bias_table, g, scale);
-        hipLaunchKernelGGL((dkv_convert_kernel<float>), cgrid, cblock, 0, s, dkv_f32, (float*)dqkv, Ttok, (int)C);
+        dkv_convert_kernel<float><<<cgrid, cblock, 0, s>>>(dkv_f32, (float*)dqkv, Ttok, (int)C);
     }
     return mtp_launch_status();
 }

@@ -24,8 +24,6 @@
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kMaxBlocks = 2048;
 constexpr int kTile = 256;          // gts per LDS tile of the assignment
 constexpr int kMaxNms = 32768;      // 512 mask words per row
 
@@ -338,11 +336,6 @@ __global__ void __launch_bounds__(kThreads) assign_phase2_kernel(const float* __
     }
 }
 
-inline unsigned grid_capped(int64_t n) {
-    const int64_t g = (n + kThreads - 1) / kThreads;
-    return (unsigned)(g < kMaxBlocks ? g : kMaxBlocks);
-}
-
 }  // namespace
 
 // ======================================================================================================================== C ABI
@@ -351,7 +344,7 @@ extern "C" int mtp_box_iou(const float* boxes1, const float* boxes2, float* out,
     MTP_CHECK_ARG(boxes1 && boxes2 && out && M > 0 && N > 0 && (kind == MTP_BOX_ALIGNED || kind == MTP_BOX_ROTATED));
     MTP_CHECK_ARG((!aligned || M == N) && M < ((int64_t)1 << 40) / N && eps >= 0.0f);
     hipStream_t s = (hipStream_t)stream;
-    const unsigned g = grid_capped(aligned ? M : M * N);
+    const unsigned g = blocks_for(aligned ? M : M * N, kThreads, kMaxBlocks);
     if (kind == MTP_BOX_ALIGNED) box_iou_kernel<0><<<g, kThreads, 0, s>>>(boxes1, boxes2, out, M, N, iof != 0, aligned != 0, eps);
     else box_iou_kernel<1><<<g, kThreads, 0, s>>>(boxes1, boxes2, out, M, N, iof != 0, aligned != 0, eps);
     return mtp_launch_status();
@@ -379,7 +372,7 @@ extern "C" int mtp_nms_scan(const void* mask, int64_t n, int64_t max_keep, int64
 template <int CALC>
 static int assign_launch(const float* gts, const float* priors, const int64_t* gt_labels, int K, int64_t N, AssignThr thr, int low_quality, int assign_all,
                          int64_t* gt_inds, float* max_overlaps, int64_t* labels, unsigned long long* key, hipStream_t s) {
-    const unsigned g = (unsigned)((N + kThreads - 1) / kThreads);
+    const unsigned g = blocks_exact(N);
     const hipError_t e = hipMemsetAsync(key, 0, (size_t)K * 8, s);
     if (e != hipSuccess) return (int)e;
     assign_phase1_kernel<CALC><<<g, kThreads, 0, s>>>(gts, priors, gt_labels, K, N, thr, gt_inds, max_overlaps, labels, key);

@@ -13,12 +13,8 @@
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / MTP_WAVE;
-constexpr int kMaxBlocks = 2048;      // memory-bound passes: 256 CUs x 8 workgroups, the rest by grid stride
 constexpr int kMaxTopk = 8;
-
-inline bool dt_ok(int dt) { return dt == MTP_F32 || dt == MTP_BF16; }
 
 __device__ __forceinline__ int wave_sum_i(int v) {
 #pragma unroll
@@ -236,11 +232,6 @@ __global__ void __launch_bounds__(kThreads) cls_hits_kernel(const float* __restr
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&counters[topk.n], (unsigned long long)N);
 }
 
-inline unsigned grid_capped(int64_t n) {
-    const int64_t g = (n + kThreads - 1) / kThreads;
-    return (unsigned)(g < kMaxBlocks ? g : kMaxBlocks);
-}
-
 }  // namespace
 
 // ======================================================================================================================== C ABI
@@ -251,7 +242,7 @@ extern "C" int mtp_gap_fwd(const void* x, int dtype, float* pooled, int64_t N, i
     const int64_t rows = N * C;
     hipStream_t s = (hipStream_t)stream;
     const bool narrow = HW * (dtype == MTP_F32 ? 4 : 2) <= 512;      // at most two 16-byte chunks per lane of a 16-lane group
-    const unsigned g = grid_capped(rows * (narrow ? 16 : 64));
+    const unsigned g = blocks_for(rows * (narrow ? 16 : 64), kThreads, kMaxBlocks);
     if (dtype == MTP_F32) {
         if (narrow) gap_fwd_kernel<float, 16><<<g, kThreads, 0, s>>>((const float*)x, pooled, rows, HW);
         else gap_fwd_kernel<float, 64><<<g, kThreads, 0, s>>>((const float*)x, pooled, rows, HW);
@@ -268,8 +259,8 @@ extern "C" int mtp_gap_bwd(const float* dpooled, void* dx, int dtype, int64_t N,
     MTP_CHECK_ARG(((uintptr_t)dx & 15) == 0 && ((uintptr_t)dpooled & 3) == 0);
     const int64_t total = N * C * HW;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == MTP_F32) gap_bwd_kernel<float><<<grid_capped((total + 3) / 4), kThreads, 0, s>>>(dpooled, (float*)dx, total, HW);
-    else gap_bwd_kernel<bf16_t><<<grid_capped((total + 7) / 8), kThreads, 0, s>>>(dpooled, (bf16_t*)dx, total, HW);
+    if (dtype == MTP_F32) gap_bwd_kernel<float><<<blocks_for((total + 3) / 4, kThreads, kMaxBlocks), kThreads, 0, s>>>(dpooled, (float*)dx, total, HW);
+    else gap_bwd_kernel<bf16_t><<<blocks_for((total + 7) / 8, kThreads, kMaxBlocks), kThreads, 0, s>>>(dpooled, (bf16_t*)dx, total, HW);
     return mtp_launch_status();
 }
 
@@ -293,7 +284,7 @@ extern "C" int mtp_cls_ce(const float* pooled, const float* w, const float* b, c
 extern "C" int mtp_cls_head_bwd(const float* dlogits, const float* pooled, const float* w, float* dw, float* db, float* dpooled, int64_t N, int64_t C,
                                 int64_t K, int accumulate, mtp_stream_t stream) {
     MTP_CHECK_ARG(dlogits && pooled && w && dw && db && N > 0 && C > 0 && K > 0 && N < INT32_MAX && C < INT32_MAX && K < INT32_MAX);
-    cls_head_bwd_kernel<<<grid_capped(K * C + (dpooled ? N * C : 0) + K), kThreads, 0, (hipStream_t)stream>>>(dlogits, pooled, w, dw, db, dpooled, (int)N,
+    cls_head_bwd_kernel<<<blocks_for(K * C + (dpooled ? N * C : 0) + K, kThreads, kMaxBlocks), kThreads, 0, (hipStream_t)stream>>>(dlogits, pooled, w, dw, db, dpooled, (int)N,
                                                                                                                (int)C, (int)K, accumulate);
     return mtp_launch_status();
 }
@@ -305,8 +296,7 @@ extern "C" int mtp_cls_hits(const float* scores, const int64_t* labels, int64_t 
     t.n = nk;
     for (int i = 0; i < kMaxTopk; ++i) t.k[i] = i < nk ? topk[i] : 0;
     for (int i = 0; i < nk; ++i) MTP_CHECK_ARG(t.k[i] >= 1 && t.k[i] <= K && (i == 0 || t.k[i] > t.k[i - 1]));
-    const int64_t g = (N + kWaves - 1) / kWaves;
-    cls_hits_kernel<<<(unsigned)(g < kMaxBlocks ? g : kMaxBlocks), kThreads, 0, (hipStream_t)stream>>>(scores, labels, N, (int)K, t, thr, use_thr,
+    cls_hits_kernel<<<blocks_for(N, kWaves, kMaxBlocks), kThreads, 0, (hipStream_t)stream>>>(scores, labels, N, (int)K, t, thr, use_thr,
                                                                                                      reinterpret_cast<unsigned long long*>(counters));
     return mtp_launch_status();
 }

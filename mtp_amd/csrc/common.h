@@ -79,6 +79,20 @@ __device__ __forceinline__ void store8(bf16_t* p, const float (&o)[8]) {
     *reinterpret_cast<uint4*>(p) = make_uint4(pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]), pack_bf16x2(o[4], o[5]), pack_bf16x2(o[6], o[7]));
 }
 
+// the same through a typed view of a void* kernel parameter at element index i (the head kernels take void* and a template dtype)
+template <typename T>
+__device__ __forceinline__ float ld1(const void* p, int64_t i) { return Elem<T>::load(reinterpret_cast<const T*>(p) + i); }
+template <typename T>
+__device__ __forceinline__ float4 ld4(const void* p, int64_t i) { return load4(reinterpret_cast<const T*>(p) + i); }
+template <typename T>
+__device__ __forceinline__ void st4(void* p, int64_t i, float4 v) { store4(reinterpret_cast<T*>(p) + i, v); }
+
+__device__ __forceinline__ float4 f4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+__device__ __forceinline__ float4 f4scale(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
+__device__ __forceinline__ float4 f4fma(float4 a, float s, float4 acc) {
+    return make_float4(fmaf(a.x, s, acc.x), fmaf(a.y, s, acc.y), fmaf(a.z, s, acc.z), fmaf(a.w, s, acc.w));
+}
+
 // 16-byte load that is guaranteed to be a global_load (not flat_load): needed when the pointer comes out of a select
 // (a flat load also counts on lgkmcnt and forces a vmcnt(0) before the next LDS access)
 __device__ __forceinline__ uint4 ldg16(const void* p) {
@@ -207,11 +221,19 @@ static inline int mtp_optin_lds(const void* kern, int bytes, unsigned long long&
 // dispatch sizes tiles, strips and persistent grids by it (a 128-CU stream runs M / 2 rows with the tile quantisation of M rows on 256 CUs).
 int mtp_stream_cus(hipStream_t stream);
 
-// grid size of a grid-stride kernel: ceil(n / per_block) workgroups, at least 1 and at most `cap`
+// workgroup size of every kernel that is not an MFMA tile (four waves), and the grid cap of the memory-bound grid-stride passes of the head files
+// (256 CUs x 8 workgroups, the rest by grid stride)
+constexpr int kThreads = 256;
+constexpr int kMaxBlocks = 2048;
+
+// The two grid helpers.  blocks_for is for GRID-STRIDE kernels only: ceil(n / per_block) workgroups, at least 1 and at most `cap`, the rest of
+// the elements by the kernel's own loop.  blocks_exact is for kernels that take one element (group) per thread and return past `n`: exactly
+// ceil(n / kThreads) workgroups, never capped -- a cap under such a kernel silently drops the tail.
 static inline unsigned blocks_for(int64_t n, int per_block, int64_t cap = 1 << 20) {
     int64_t b = (n + per_block - 1) / per_block;
     return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
 }
+static inline unsigned blocks_exact(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
 // The 7 x 7 windows of an RVSA block over an (Hp, Wp) token map: zero padding to multiples of 7, split evenly with the odd row / column at
 // the bottom / right (VIT:229-230).  ONE definition for the attention kernels (make_geom), the sampling heads and the windowed LayerNorm
@@ -229,3 +251,28 @@ static inline int mtp_launch_status() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }
+
+// ---- dtype dispatch of the entry points: ONE place that maps an MTP_* dtype to the element type of a kernel template -----------------------------
+static inline bool dt_ok(int dtype) { return dtype == MTP_F32 || dtype == MTP_BF16; }
+
+// One activation dtype.  `launch` is a generic lambda called with a value of the element type:
+//     return for_act(dtype, [&](auto t) { using T = decltype(t); kernel<T><<<grid, kThreads, 0, s>>>((const T*)x, ...); });
+// Any other dtype: MTP_ERR_UNSUPPORTED and nothing launched; otherwise the status of what `launch` launched.
+template <typename F>
+static inline int for_act(int dtype, F&& launch) {
+    if (dtype == MTP_BF16) launch(bf16_t{});
+    else if (dtype == MTP_F32) launch(float{});
+    else return MTP_ERR_UNSUPPORTED;
+    return mtp_launch_status();
+}
+
+// Two independent activation dtypes, all four combinations, with TA / TB named in the statement.  (A pair site that instantiates only some of the
+// combinations keeps its own ladder: this one would add kernels to the code object.)
+#define MTP_DISPATCH2(DT_A, DT_B, ...)                                                                        \
+    do {                                                                                                      \
+        if (!dt_ok(DT_A) || !dt_ok(DT_B)) return MTP_ERR_UNSUPPORTED;                                         \
+        if ((DT_A) == MTP_F32 && (DT_B) == MTP_F32) { using TA = float; using TB = float; __VA_ARGS__; }      \
+        else if ((DT_A) == MTP_F32) { using TA = float; using TB = bf16_t; __VA_ARGS__; }                     \
+        else if ((DT_B) == MTP_F32) { using TA = bf16_t; using TB = float; __VA_ARGS__; }                     \
+        else { using TA = bf16_t; using TB = bf16_t; __VA_ARGS__; }                                           \
+    } while (0)

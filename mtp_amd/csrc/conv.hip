@@ -258,22 +258,51 @@ __global__ __launch_bounds__(256) void dwconv3x3_p8_kernel(const bf16_t* __restr
     }
 }
 
+// The frame the two weight-gradient kernels below share: a block = 256 threads = (64 channel quads cq) x (4 pixel lanes pl) over the pixels
+// [p0, p1) of blockIdx.y; each lane keeps 40 sums (4 channels x 9 taps, then the 4 bias sums), the four pixel lanes are added through LDS in a fixed order.
+struct DwLane {
+    int cq, pl, c, cc;      // cc = c clamped into the map (the loads of a lane past C are unconditional, its sums are dropped)
+    bool cok;
+    int64_t p0, p1;
+};
+__device__ __forceinline__ DwLane dw_lane(int C, int64_t pixels, int64_t pix_per_block) {
+    DwLane l;
+    l.cq = threadIdx.x & 63; l.pl = threadIdx.x >> 6;
+    l.c = 4 * ((int)blockIdx.x * 64 + l.cq);
+    l.cok = l.c < C;
+    l.cc = l.cok ? l.c : 0;
+    l.p0 = (int64_t)blockIdx.y * pix_per_block;
+    const int64_t p1 = l.p0 + pix_per_block;
+    l.p1 = p1 < pixels ? p1 : pixels;
+    return l;
+}
+__device__ __forceinline__ void dw_reduce_store(float (&red)[4][64][40], const float (&acc)[40], const DwLane& l, float* __restrict__ part, int C) {
+#pragma unroll
+    for (int i = 0; i < 40; ++i) red[l.pl][l.cq][i] = acc[i];
+    __syncthreads();
+    if (l.pl == 0 && l.cok) {
+        float* out = part + (int64_t)blockIdx.y * (10 * (int64_t)C);
+#pragma unroll
+        for (int i = 0; i < 40; ++i) {
+            const float s = (red[0][l.cq][i] + red[1][l.cq][i]) + (red[2][l.cq][i] + red[3][l.cq][i]);
+            if (i < 36) out[(l.c + i / 9) * 9 + i % 9] = s;
+            else out[9 * (int64_t)C + l.c + (i - 36)] = s;
+        }
+    }
+}
+
 // weight / bias gradient partials: part[block][c * 9 + tap] = sum over the block's pixels of dy[pix][c] x[pix + tap][c],
 // part[block][9 C + c] = sum dy[pix][c].  Block = 256 threads = (64 channel quads) x (4 pixel lanes); reduced through LDS.
 template <typename T>
 __global__ __launch_bounds__(256) void dwconv3x3_dw_kernel(const T* __restrict__ dy, const T* __restrict__ x, float* __restrict__ part,
                                                           int H, int W, int C, int64_t pixels, int64_t pix_per_block) {
     __shared__ float red[4][64][40];
-    const int cq = threadIdx.x & 63, pl = threadIdx.x >> 6;
-    const int c = 4 * ((int)blockIdx.x * 64 + cq);
-    const bool cok = c < C;
-    const int cc = cok ? c : 0;
+    const DwLane l = dw_lane(C, pixels, pix_per_block);
+    const int pl = l.pl, cc = l.cc;
+    const int64_t p0 = l.p0, p1 = l.p1;
     float acc[40];
 #pragma unroll
     for (int i = 0; i < 40; ++i) acc[i] = 0.f;
-    const int64_t p0 = (int64_t)blockIdx.y * pix_per_block;
-    int64_t p1 = p0 + pix_per_block;
-    p1 = p1 < pixels ? p1 : pixels;
     // (wx, h) of the lane's first pixel once, then stepped: two 64-bit divisions per pixel were most of the loop's instructions
     int wx = (int)((p0 + pl) % W), h = (int)(((p0 + pl) / W) % H);
     for (int64_t pix = p0 + pl; pix < p1; pix += 4, wx += 4) {
@@ -297,18 +326,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_dw_kernel(const T* __restrict__
             }
         }
     }
-#pragma unroll
-    for (int i = 0; i < 40; ++i) red[pl][cq][i] = acc[i];
-    __syncthreads();
-    if (pl == 0 && cok) {
-        float* out = part + (int64_t)blockIdx.y * (10 * (int64_t)C);
-#pragma unroll
-        for (int i = 0; i < 40; ++i) {
-            const float s = (red[0][cq][i] + red[1][cq][i]) + (red[2][cq][i] + red[3][cq][i]);
-            if (i < 36) out[(c + i / 9) * 9 + i % 9] = s;
-            else out[9 * (int64_t)C + c + (i - 36)] = s;
-        }
-    }
+    dw_reduce_store(red, acc, l, part, C);
 }
 
 // the same partials with P consecutive pixels of a row per step (round 5; bf16, W % P == 0, pix_per_block % P == 0): P gradient loads + the 3 x (P + 2) window -- 22 loads for
@@ -317,16 +335,12 @@ template <int P>
 __global__ __launch_bounds__(256) void dwconv3x3_dw_px_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, float* __restrict__ part,
                                                              int H, int W, int C, int64_t pixels, int64_t pix_per_block) {
     __shared__ float red[4][64][40];
-    const int cq = threadIdx.x & 63, pl = threadIdx.x >> 6;
-    const int c = 4 * ((int)blockIdx.x * 64 + cq);
-    const bool cok = c < C;
-    const int cc = cok ? c : 0;
+    const DwLane l = dw_lane(C, pixels, pix_per_block);
+    const int pl = l.pl, cc = l.cc;
+    const int64_t p0 = l.p0, p1 = l.p1;
     float acc[40];
 #pragma unroll
     for (int i = 0; i < 40; ++i) acc[i] = 0.f;
-    const int64_t p0 = (int64_t)blockIdx.y * pix_per_block;
-    int64_t p1 = p0 + pix_per_block;
-    p1 = p1 < pixels ? p1 : pixels;
     for (int64_t pix = p0 + P * pl; pix < p1; pix += 4 * P) {      // (pix % P == 0 and W % P == 0: the P pixels lie in one row)
         const int wx0 = (int)(pix % W), h = (int)((pix / W) % H);
         uint2 gr[P], raw[3][P + 2];
@@ -367,18 +381,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_dw_px_kernel(const bf16_t* __re
             }
         }
     }
-#pragma unroll
-    for (int i = 0; i < 40; ++i) red[pl][cq][i] = acc[i];
-    __syncthreads();
-    if (pl == 0 && cok) {
-        float* out = part + (int64_t)blockIdx.y * (10 * (int64_t)C);
-#pragma unroll
-        for (int i = 0; i < 40; ++i) {
-            const float sum = (red[0][cq][i] + red[1][cq][i]) + (red[2][cq][i] + red[3][cq][i]);
-            if (i < 36) out[(c + i / 9) * 9 + i % 9] = sum;
-            else out[9 * (int64_t)C + c + (i - 36)] = sum;
-        }
-    }
+    dw_reduce_store(red, acc, l, part, C);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -500,8 +503,6 @@ __global__ __launch_bounds__(256) void copy_rows_kernel(const T* __restrict__ sr
     const int64_t r = idx / n, c = idx - r * n;
     dst[r * dst_ld + c] = src[r * src_ld + c];
 }
-
-inline unsigned blocks_for(int64_t total) { return (unsigned)((total + 255) / 256); }
 
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -631,20 +632,23 @@ int col2im3x3_family(const void* dcols, int cols_dtype, const float* dx, int64_t
                      int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t stride, int64_t Kp) {
     if (!dcols || !dx || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || stride < 1 || Kp < 9 * Cin) return MTP_ERR_ARG;
     if (cols_dtype == MTP_BF16 && sC == 1 && !(Cin & 7) && !(Kp & 7) && !((sN | sH | sW) & 7) && !(((uintptr_t)dcols | (uintptr_t)dx) & 15)) return MTP_CONV_KERNEL_V8;
-    return (cols_dtype == MTP_BF16 || cols_dtype == MTP_F32) ? MTP_CONV_KERNEL_ELEMENT : MTP_CONV_KERNEL_NONE;
+    return dt_ok(cols_dtype) ? MTP_CONV_KERNEL_ELEMENT : MTP_CONV_KERNEL_NONE;
 }
 // forward (bias may be NULL) and data gradient (bias = NULL): x resp. dy, w, y resp. dx
 int dwconv3x3_family(const void* x, const float* w, const float* bias, const void* y, int dtype, int64_t N, int64_t H, int64_t W, int64_t C) {
     if (!x || !w || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 4)) return MTP_ERR_ARG;
     if (N * H * W * (C / 4) >= ((int64_t)1 << 31)) return MTP_CONV_KERNEL_NONE;      // 32-bit index arithmetic in the kernels
     if (dtype == MTP_BF16 && !(W & 7) && !(((uintptr_t)w | (uintptr_t)(bias ? bias : w)) & 15)) return MTP_CONV_KERNEL_P8;
-    return (dtype == MTP_BF16 || dtype == MTP_F32) ? MTP_CONV_KERNEL_ELEMENT : MTP_CONV_KERNEL_NONE;
+    return dt_ok(dtype) ? MTP_CONV_KERNEL_ELEMENT : MTP_CONV_KERNEL_NONE;
 }
 int dwconv3x3_dw_family(const void* dy, const void* x, int dtype, const float* part, int64_t N, int64_t H, int64_t W, int64_t C) {
     if (!dy || !x || !part || N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 4)) return MTP_ERR_ARG;
     if (dtype == MTP_BF16 && !(W & 3)) return MTP_CONV_KERNEL_PX4;
-    return (dtype == MTP_BF16 || dtype == MTP_F32) ? MTP_CONV_KERNEL_ELEMENT : MTP_CONV_KERNEL_NONE;
+    return dt_ok(dtype) ? MTP_CONV_KERNEL_ELEMENT : MTP_CONV_KERNEL_NONE;
 }
+
+// what an entry point returns instead of launching: the family's own error, MTP_ERR_UNSUPPORTED where no kernel covers the call, 0 = launch
+inline int family_refusal(int fam) { return fam < 0 ? fam : fam == MTP_CONV_KERNEL_NONE ? MTP_ERR_UNSUPPORTED : 0; }
 
 }  // namespace
 
@@ -663,102 +667,95 @@ extern "C" int mtp_conv_kernel(int op, const void* src, int src_dtype, int64_t s
 extern "C" int mtp_im2col3x3(const void* x, int x_dtype, int64_t sN, int64_t sH, int64_t sW, int64_t sC, void* cols, int cols_dtype,
                              int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t stride, int64_t Kp, mtp_stream_t stream) {
     const int fam = im2col3x3_family(x, x_dtype, sN, sH, sW, sC, cols, cols_dtype, N, H, W, Cin, stride, Kp);
-    if (fam < 0) return fam;
-    if (fam == MTP_CONV_KERNEL_NONE) return MTP_ERR_UNSUPPORTED;
+    if (const int rc = family_refusal(fam)) return rc;
     const int Ho = (int)((H - 1) / stride + 1), Wo = (int)((W - 1) / stride + 1);      // (H + 2 - 3) / s + 1
     const int64_t total = N * Ho * Wo * Kp;
     hipStream_t s = (hipStream_t)stream;
     if (fam == MTP_CONV_KERNEL_V8) {
         const int64_t total8 = total / 8;
-        hipLaunchKernelGGL(im2col3x3_v8_kernel, dim3(blocks_for(total8)), dim3(256), 0, s, (const bf16_t*)x, sN, sH, sW, (bf16_t*)cols, (int)H, (int)W, (int)Cin, Ho, Wo, (int)stride, (int)Kp, total8);
+        im2col3x3_v8_kernel<<<blocks_exact(total8), kThreads, 0, s>>>((const bf16_t*)x, sN, sH, sW, (bf16_t*)cols, (int)H, (int)W, (int)Cin, Ho, Wo, (int)stride, (int)Kp, total8);
         return mtp_launch_status();
     }
-    const dim3 grid(blocks_for(total)), block(256);
-#define MTP_LAUNCH_I2C(TX, TC) hipLaunchKernelGGL((im2col3x3_kernel<TX, TC>), grid, block, 0, s, (const TX*)x, sN, sH, sW, sC, (TC*)cols, (int)H, (int)W, (int)Cin, Ho, Wo, (int)stride, (int)Kp, total)
-    if (x_dtype == MTP_F32 && cols_dtype == MTP_F32) MTP_LAUNCH_I2C(float, float);
-    else if (x_dtype == MTP_F32 && cols_dtype == MTP_BF16) MTP_LAUNCH_I2C(float, bf16_t);
-    else MTP_LAUNCH_I2C(bf16_t, bf16_t);
-#undef MTP_LAUNCH_I2C
+    // three of the four pairs exist (no bf16 -> f32), so this site keeps its own ladder; the family has refused everything else
+    auto launch = [&](auto tx, auto tc) {
+        using TX = decltype(tx);
+        using TC = decltype(tc);
+        im2col3x3_kernel<TX, TC><<<blocks_exact(total), kThreads, 0, s>>>((const TX*)x, sN, sH, sW, sC, (TC*)cols, (int)H, (int)W, (int)Cin, Ho, Wo, (int)stride, (int)Kp, total);
+    };
+    if (x_dtype == MTP_F32 && cols_dtype == MTP_F32) launch(float{}, float{});
+    else if (x_dtype == MTP_F32) launch(float{}, bf16_t{});
+    else launch(bf16_t{}, bf16_t{});
     return mtp_launch_status();
 }
 
 extern "C" int mtp_col2im3x3(const void* dcols, int cols_dtype, float* dx, int64_t sN, int64_t sH, int64_t sW, int64_t sC,
                              int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t stride, int64_t Kp, int accumulate, mtp_stream_t stream) {
     const int fam = col2im3x3_family(dcols, cols_dtype, dx, sN, sH, sW, sC, N, H, W, Cin, stride, Kp);
-    if (fam < 0) return fam;
-    if (fam == MTP_CONV_KERNEL_NONE) return MTP_ERR_UNSUPPORTED;
+    if (const int rc = family_refusal(fam)) return rc;
     const int Ho = (int)((H - 1) / stride + 1), Wo = (int)((W - 1) / stride + 1);
     const int64_t total = N * H * W * Cin;
     hipStream_t s = (hipStream_t)stream;
     if (fam == MTP_CONV_KERNEL_V8) {
         const int64_t total8 = total / 8;
-        hipLaunchKernelGGL(col2im3x3_v8_kernel, dim3(blocks_for(total8)), dim3(256), 0, s, (const bf16_t*)dcols, dx, sN, sH, sW, (int)H, (int)W, (int)Cin, Ho, Wo, (int)stride, (int)Kp, accumulate, total8);
+        col2im3x3_v8_kernel<<<blocks_exact(total8), kThreads, 0, s>>>((const bf16_t*)dcols, dx, sN, sH, sW, (int)H, (int)W, (int)Cin, Ho, Wo, (int)stride, (int)Kp, accumulate, total8);
         return mtp_launch_status();
     }
-    const dim3 grid(blocks_for(total)), block(256);
-    if (cols_dtype == MTP_BF16)
-        hipLaunchKernelGGL((col2im3x3_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)dcols, dx, sN, sH, sW, sC, (int)H, (int)W, (int)Cin, Ho, Wo, (int)stride, (int)Kp, accumulate, total);
-    else
-        hipLaunchKernelGGL((col2im3x3_kernel<float>), grid, block, 0, s, (const float*)dcols, dx, sN, sH, sW, sC, (int)H, (int)W, (int)Cin, Ho, Wo, (int)stride, (int)Kp, accumulate, total);
-    return mtp_launch_status();
+    return for_act(cols_dtype, [&](auto t) {
+        using T = decltype(t);
+        col2im3x3_kernel<T><<<blocks_exact(total), kThreads, 0, s>>>((const T*)dcols, dx, sN, sH, sW, sC, (int)H, (int)W, (int)Cin, Ho, Wo, (int)stride, (int)Kp, accumulate, total);
+    });
 }
 
 extern "C" int mtp_conv3x3_pack(const float* w, void* w2, void* w2t, int dtype, int64_t Cout, int64_t Cin, int64_t Kp, mtp_stream_t stream) {
     if (!w || (!w2 && !w2t) || Cout <= 0 || Cin <= 0 || Kp < 9 * Cin) return MTP_ERR_ARG;
-    const dim3 grid(blocks_for(Cout * Kp)), block(256);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == MTP_BF16) hipLaunchKernelGGL((conv3x3_pack_kernel<bf16_t>), grid, block, 0, s, w, (bf16_t*)w2, (bf16_t*)w2t, (int)Cout, (int)Cin, (int)Kp);
-    else if (dtype == MTP_F32) hipLaunchKernelGGL((conv3x3_pack_kernel<float>), grid, block, 0, s, w, (float*)w2, (float*)w2t, (int)Cout, (int)Cin, (int)Kp);
-    else return MTP_ERR_UNSUPPORTED;
-    return mtp_launch_status();
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        conv3x3_pack_kernel<T><<<blocks_exact(Cout * Kp), kThreads, 0, (hipStream_t)stream>>>(w, (T*)w2, (T*)w2t, (int)Cout, (int)Cin, (int)Kp);
+    });
 }
 
 extern "C" int mtp_conv3x3_unpack_grad(const float* dw2, float* dw, int64_t Cout, int64_t Cin, int64_t Kp, mtp_stream_t stream) {
     if (!dw2 || !dw || Cout <= 0 || Cin <= 0 || Kp < 9 * Cin) return MTP_ERR_ARG;
-    hipLaunchKernelGGL(conv3x3_unpack_kernel, dim3(blocks_for(Cout * Cin * 9)), dim3(256), 0, (hipStream_t)stream, dw2, dw, (int)Cout, (int)Cin, (int)Kp);
+    conv3x3_unpack_kernel<<<blocks_exact(Cout * Cin * 9), kThreads, 0, (hipStream_t)stream>>>(dw2, dw, (int)Cout, (int)Cin, (int)Kp);
     return mtp_launch_status();
 }
 
 extern "C" int mtp_pack_rows_padded(const float* w, void* wp, void* wpt, int dtype, int64_t R, int64_t C, int64_t Rp, mtp_stream_t stream) {
     if (!w || (!wp && !wpt) || R <= 0 || C <= 0 || Rp < R) return MTP_ERR_ARG;
-    const dim3 grid(blocks_for(Rp * C)), block(256);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == MTP_BF16) hipLaunchKernelGGL((pack_rows_padded_kernel<bf16_t>), grid, block, 0, s, w, (bf16_t*)wp, (bf16_t*)wpt, (int)R, (int)C, (int)Rp);
-    else if (dtype == MTP_F32) hipLaunchKernelGGL((pack_rows_padded_kernel<float>), grid, block, 0, s, w, (float*)wp, (float*)wpt, (int)R, (int)C, (int)Rp);
-    else return MTP_ERR_UNSUPPORTED;
-    return mtp_launch_status();
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        pack_rows_padded_kernel<T><<<blocks_exact(Rp * C), kThreads, 0, (hipStream_t)stream>>>(w, (T*)wp, (T*)wpt, (int)R, (int)C, (int)Rp);
+    });
 }
 
 extern "C" int mtp_dwconv3x3_fwd(const void* x, const float* w, const float* bias, void* y, int dtype, int64_t N, int64_t H, int64_t W, int64_t C, mtp_stream_t stream) {
     const int fam = dwconv3x3_family(x, w, bias, y, dtype, N, H, W, C);
-    if (fam < 0) return fam;
-    if (fam == MTP_CONV_KERNEL_NONE) return MTP_ERR_UNSUPPORTED;
+    if (const int rc = family_refusal(fam)) return rc;
     const int64_t total = N * H * W * (C / 4);
-    const dim3 grid(blocks_for(total)), block(256);
     hipStream_t s = (hipStream_t)stream;
     if (fam == MTP_CONV_KERNEL_P8) {
-        hipLaunchKernelGGL((dwconv3x3_p8_kernel<bf16_t, false>), dim3(blocks_for(total / 8)), block, 0, s, (const bf16_t*)x, w, bias, (bf16_t*)y, (int)H, (int)W, (int)C, 0, total / 8);
+        dwconv3x3_p8_kernel<bf16_t, false><<<blocks_exact(total / 8), kThreads, 0, s>>>((const bf16_t*)x, w, bias, (bf16_t*)y, (int)H, (int)W, (int)C, 0, total / 8);
         return mtp_launch_status();
     }
-    if (dtype == MTP_BF16) hipLaunchKernelGGL((dwconv3x3_kernel<bf16_t, bf16_t, false>), grid, block, 0, s, (const bf16_t*)x, w, bias, (bf16_t*)y, (int)H, (int)W, (int)C, 0, total);
-    else hipLaunchKernelGGL((dwconv3x3_kernel<float, float, false>), grid, block, 0, s, (const float*)x, w, bias, (float*)y, (int)H, (int)W, (int)C, 0, total);
-    return mtp_launch_status();
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        dwconv3x3_kernel<T, T, false><<<blocks_exact(total), kThreads, 0, s>>>((const T*)x, w, bias, (T*)y, (int)H, (int)W, (int)C, 0, total);
+    });
 }
 
 extern "C" int mtp_dwconv3x3_bwd_dx(const void* dy, int dtype, const float* w, float* dx, int accumulate, int64_t N, int64_t H, int64_t W, int64_t C, mtp_stream_t stream) {
     const int fam = dwconv3x3_family(dy, w, nullptr, dx, dtype, N, H, W, C);
-    if (fam < 0) return fam;
-    if (fam == MTP_CONV_KERNEL_NONE) return MTP_ERR_UNSUPPORTED;
+    if (const int rc = family_refusal(fam)) return rc;
     const int64_t total = N * H * W * (C / 4);
-    const dim3 grid(blocks_for(total)), block(256);
     hipStream_t s = (hipStream_t)stream;
     if (fam == MTP_CONV_KERNEL_P8) {
-        hipLaunchKernelGGL((dwconv3x3_p8_kernel<float, true>), dim3(blocks_for(total / 8)), block, 0, s, (const bf16_t*)dy, w, (const float*)nullptr, dx, (int)H, (int)W, (int)C, accumulate, total / 8);
+        dwconv3x3_p8_kernel<float, true><<<blocks_exact(total / 8), kThreads, 0, s>>>((const bf16_t*)dy, w, (const float*)nullptr, dx, (int)H, (int)W, (int)C, accumulate, total / 8);
         return mtp_launch_status();
     }
-    if (dtype == MTP_BF16) hipLaunchKernelGGL((dwconv3x3_kernel<bf16_t, float, true>), grid, block, 0, s, (const bf16_t*)dy, w, (const float*)nullptr, dx, (int)H, (int)W, (int)C, accumulate, total);
-    else hipLaunchKernelGGL((dwconv3x3_kernel<float, float, true>), grid, block, 0, s, (const float*)dy, w, (const float*)nullptr, dx, (int)H, (int)W, (int)C, accumulate, total);
-    return mtp_launch_status();
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        dwconv3x3_kernel<T, float, true><<<blocks_exact(total), kThreads, 0, s>>>((const T*)dy, w, (const float*)nullptr, dx, (int)H, (int)W, (int)C, accumulate, total);
+    });
 }
 
 extern "C" int64_t mtp_dwconv3x3_bwd_dw_partial_rows(int64_t N, int64_t H, int64_t W) {
@@ -770,48 +767,46 @@ extern "C" int64_t mtp_dwconv3x3_bwd_dw_partial_rows(int64_t N, int64_t H, int64
 /* part: (mtp_dwconv3x3_bwd_dw_partial_rows, 10 C) f32 = per-block partials of [dweight (C, 9) | dbias (C)] */
 extern "C" int mtp_dwconv3x3_bwd_dw(const void* dy, const void* x, int dtype, float* part, int64_t N, int64_t H, int64_t W, int64_t C, mtp_stream_t stream) {
     const int fam = dwconv3x3_dw_family(dy, x, dtype, part, N, H, W, C);
-    if (fam < 0) return fam;
-    if (fam == MTP_CONV_KERNEL_NONE) return MTP_ERR_UNSUPPORTED;
+    if (const int rc = family_refusal(fam)) return rc;
     const int64_t pixels = N * H * W, nb = mtp_dwconv3x3_bwd_dw_partial_rows(N, H, W);
     const int64_t ppb = (pixels + nb - 1) / nb;
-    const dim3 grid((unsigned)((C / 4 + 63) / 64), (unsigned)nb), block(256);
+    const dim3 grid((unsigned)((C / 4 + 63) / 64), (unsigned)nb);
     hipStream_t s = (hipStream_t)stream;
     if (fam == MTP_CONV_KERNEL_PX4) {      // blocks of whole 4-pixel groups (the last blocks may be empty: they write zero partials)
         const int64_t ppb4 = (ppb + 3) / 4 * 4;
-        hipLaunchKernelGGL(dwconv3x3_dw_px_kernel<4>, grid, block, 0, s, (const bf16_t*)dy, (const bf16_t*)x, part, (int)H, (int)W, (int)C, pixels, ppb4);
+        dwconv3x3_dw_px_kernel<4><<<grid, kThreads, 0, s>>>((const bf16_t*)dy, (const bf16_t*)x, part, (int)H, (int)W, (int)C, pixels, ppb4);
         return mtp_launch_status();
     }
-    if (dtype == MTP_BF16) hipLaunchKernelGGL((dwconv3x3_dw_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)dy, (const bf16_t*)x, part, (int)H, (int)W, (int)C, pixels, ppb);
-    else hipLaunchKernelGGL((dwconv3x3_dw_kernel<float>), grid, block, 0, s, (const float*)dy, (const float*)x, part, (int)H, (int)W, (int)C, pixels, ppb);
-    return mtp_launch_status();
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        dwconv3x3_dw_kernel<T><<<grid, kThreads, 0, s>>>((const T*)dy, (const T*)x, part, (int)H, (int)W, (int)C, pixels, ppb);
+    });
 }
 
 extern "C" int mtp_softmax_groups_fwd(const void* logits, int64_t ld, void* prob, int dtype, int64_t rows, int64_t G, int64_t P, mtp_stream_t stream) {
     if (!logits || !prob || rows <= 0 || G <= 0 || P <= 0 || P > 32 || ld < G * P) return MTP_ERR_ARG;
     const int64_t total = rows * G;
-    const dim3 grid(blocks_for(total)), block(256);
-    hipStream_t s = (hipStream_t)stream;
     if (total >= ((int64_t)1 << 31)) return MTP_ERR_UNSUPPORTED;
-#define MTP_SMX_FWD(T_, PC_) hipLaunchKernelGGL((softmax_groups_fwd_kernel<T_, PC_>), grid, block, 0, s, (const T_*)logits, ld, (T_*)prob, (int)G, (int)P, total)
-    if (dtype == MTP_BF16) { if (P == 9) MTP_SMX_FWD(bf16_t, 9); else if (P == 8) MTP_SMX_FWD(bf16_t, 8); else MTP_SMX_FWD(bf16_t, 0); }
-    else if (dtype == MTP_F32) { if (P == 9) MTP_SMX_FWD(float, 9); else if (P == 8) MTP_SMX_FWD(float, 8); else MTP_SMX_FWD(float, 0); }
-    else return MTP_ERR_UNSUPPORTED;
-#undef MTP_SMX_FWD
-    return mtp_launch_status();
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        auto launch = [&](auto kernel) { kernel<<<blocks_exact(total), kThreads, 0, (hipStream_t)stream>>>((const T*)logits, ld, (T*)prob, (int)G, (int)P, total); };
+        if (P == 9) launch(softmax_groups_fwd_kernel<T, 9>);
+        else if (P == 8) launch(softmax_groups_fwd_kernel<T, 8>);
+        else launch(softmax_groups_fwd_kernel<T, 0>);
+    });
 }
 
 extern "C" int mtp_softmax_groups_bwd(const void* prob, const float* dprob, void* dlogits, int64_t ld, int dtype, int64_t rows, int64_t G, int64_t P, mtp_stream_t stream) {
     if (!prob || !dprob || !dlogits || rows <= 0 || G <= 0 || P <= 0 || P > 32 || ld < G * P) return MTP_ERR_ARG;
     const int64_t total = rows * G;
-    const dim3 grid(blocks_for(total)), block(256);
-    hipStream_t s = (hipStream_t)stream;
     if (total >= ((int64_t)1 << 31)) return MTP_ERR_UNSUPPORTED;
-#define MTP_SMX_BWD(T_, PC_) hipLaunchKernelGGL((softmax_groups_bwd_kernel<T_, PC_>), grid, block, 0, s, (const T_*)prob, dprob, (T_*)dlogits, ld, (int)G, (int)P, total)
-    if (dtype == MTP_BF16) { if (P == 9) MTP_SMX_BWD(bf16_t, 9); else if (P == 8) MTP_SMX_BWD(bf16_t, 8); else MTP_SMX_BWD(bf16_t, 0); }
-    else if (dtype == MTP_F32) { if (P == 9) MTP_SMX_BWD(float, 9); else if (P == 8) MTP_SMX_BWD(float, 8); else MTP_SMX_BWD(float, 0); }
-    else return MTP_ERR_UNSUPPORTED;
-#undef MTP_SMX_BWD
-    return mtp_launch_status();
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        auto launch = [&](auto kernel) { kernel<<<blocks_exact(total), kThreads, 0, (hipStream_t)stream>>>((const T*)prob, dprob, (T*)dlogits, ld, (int)G, (int)P, total); };
+        if (P == 9) launch(softmax_groups_bwd_kernel<T, 9>);
+        else if (P == 8) launch(softmax_groups_bwd_kernel<T, 8>);
+        else launch(softmax_groups_bwd_kernel<T, 0>);
+    });
 }
 
 extern "C" int mtp_scale_residual_fwd(const float* x, const void* z, int dtype, const float* gamma, const float* sample_scale, int64_t rows_per_sample,
@@ -819,13 +814,11 @@ extern "C" int mtp_scale_residual_fwd(const float* x, const void* z, int dtype, 
     if (!x || !z || !gamma || !out || rows <= 0 || C <= 0 || (C % 4) || (sample_scale && rows_per_sample <= 0)) return MTP_ERR_ARG;
     const int64_t total = rows * (C / 4);
     if (total >= ((int64_t)1 << 31)) return MTP_ERR_UNSUPPORTED;      // 32-bit index arithmetic in the kernel
-    const dim3 grid(blocks_for(total)), block(256);
-    hipStream_t s = (hipStream_t)stream;
     const int rps = (int)(rows_per_sample > 0 ? rows_per_sample : 1);
-    if (dtype == MTP_BF16) hipLaunchKernelGGL((scale_residual_fwd_kernel<bf16_t>), grid, block, 0, s, x, (const bf16_t*)z, gamma, sample_scale, rps, out, (bf16_t*)out_act, (int)C, total);
-    else if (dtype == MTP_F32) hipLaunchKernelGGL((scale_residual_fwd_kernel<float>), grid, block, 0, s, x, (const float*)z, gamma, sample_scale, rps, out, (float*)out_act, (int)C, total);
-    else return MTP_ERR_UNSUPPORTED;
-    return mtp_launch_status();
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        scale_residual_fwd_kernel<T><<<blocks_exact(total), kThreads, 0, (hipStream_t)stream>>>(x, (const T*)z, gamma, sample_scale, rps, out, (T*)out_act, (int)C, total);
+    });
 }
 
 extern "C" int64_t mtp_scale_residual_bwd_partial_rows(int64_t rows) {
@@ -840,69 +833,65 @@ extern "C" int mtp_scale_residual_bwd(const float* dout, const void* z, int dtyp
     if (rows >= ((int64_t)1 << 31)) return MTP_ERR_UNSUPPORTED;
     const int64_t nb = mtp_scale_residual_bwd_partial_rows(rows);
     const int64_t rpb = (rows + nb - 1) / nb;
-    const dim3 grid((unsigned)((C / 4 + 63) / 64), (unsigned)nb), block(256);
-    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)((C / 4 + 63) / 64), (unsigned)nb);
     const int rps = (int)(rows_per_sample > 0 ? rows_per_sample : 1);
-    if (dtype == MTP_BF16) hipLaunchKernelGGL((scale_residual_bwd_kernel<bf16_t>), grid, block, 0, s, dout, (const bf16_t*)z, gamma, sample_scale, rps, (bf16_t*)dz, part, (int)C, rows, rpb);
-    else if (dtype == MTP_F32) hipLaunchKernelGGL((scale_residual_bwd_kernel<float>), grid, block, 0, s, dout, (const float*)z, gamma, sample_scale, rps, (float*)dz, part, (int)C, rows, rpb);
-    else return MTP_ERR_UNSUPPORTED;
-    return mtp_launch_status();
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        scale_residual_bwd_kernel<T><<<grid, kThreads, 0, (hipStream_t)stream>>>(dout, (const T*)z, gamma, sample_scale, rps, (T*)dz, part, (int)C, rows, rpb);
+    });
 }
 
 extern "C" int mtp_cast_pad_rows(const float* src, int64_t n, void* dst, int dst_dtype, int64_t ld, int64_t rows, mtp_stream_t stream) {
     if (!src || !dst || n <= 0 || ld < n || rows <= 0) return MTP_ERR_ARG;
     const int64_t total = rows * ld;
-    const dim3 grid(blocks_for(total)), block(256);
-    hipStream_t s = (hipStream_t)stream;
-    if (dst_dtype == MTP_BF16) hipLaunchKernelGGL((cast_pad_rows_kernel<bf16_t>), grid, block, 0, s, src, n, (bf16_t*)dst, ld, total);
-    else if (dst_dtype == MTP_F32) hipLaunchKernelGGL((cast_pad_rows_kernel<float>), grid, block, 0, s, src, n, (float*)dst, ld, total);
-    else return MTP_ERR_UNSUPPORTED;
-    return mtp_launch_status();
+    return for_act(dst_dtype, [&](auto t) {
+        using T = decltype(t);
+        cast_pad_rows_kernel<T><<<blocks_exact(total), kThreads, 0, (hipStream_t)stream>>>(src, n, (T*)dst, ld, total);
+    });
 }
 
 extern "C" int mtp_copy_rows(const void* src, int64_t src_ld, void* dst, int64_t dst_ld, int dtype, int64_t n, int64_t rows, mtp_stream_t stream) {
     if (!src || !dst || n <= 0 || src_ld < n || dst_ld < n || rows <= 0) return MTP_ERR_ARG;
     const int64_t total = rows * n;
-    const dim3 grid(blocks_for(total)), block(256);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == MTP_BF16) hipLaunchKernelGGL((copy_rows_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)src, src_ld, (bf16_t*)dst, dst_ld, n, total);
-    else if (dtype == MTP_F32) hipLaunchKernelGGL((copy_rows_kernel<float>), grid, block, 0, s, (const float*)src, src_ld, (float*)dst, dst_ld, n, total);
-    else return MTP_ERR_UNSUPPORTED;
-    return mtp_launch_status();
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        copy_rows_kernel<T><<<blocks_exact(total), kThreads, 0, (hipStream_t)stream>>>((const T*)src, src_ld, (T*)dst, dst_ld, n, total);
+    });
 }
 
 /* ---- depth-wise k x k convolution, any odd k (InternImage-H/G: dw_kernel_size, ops_dcnv3/modules/dcnv3.py:124,146-151) -- the plain forms; k = 3 callers use the
  * mtp_dwconv3x3_* entries.  w (C, 1, k, k) f32.  bwd_dw ACCUMULATES into dw / db (f32 atomics): clear them first. */
+// the three operands every one of them needs, the map and the tap count
+static bool dwconvk_args_ok(const void* a, const void* b, const void* c, int64_t N, int64_t H, int64_t W, int64_t C, int k) {
+    return a && b && c && N > 0 && H > 0 && W > 0 && C > 0 && !(C % 4) && k >= 1 && (k & 1) && k <= 15;
+}
 extern "C" int mtp_dwconv_fwd(const void* x, const float* w, const float* bias, void* y, int dtype, int64_t N, int64_t H, int64_t W, int64_t C, int k, mtp_stream_t stream) {
-    if (!x || !w || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 4) || k < 1 || !(k & 1) || k > 15) return MTP_ERR_ARG;
+    if (!dwconvk_args_ok(x, w, y, N, H, W, C, k)) return MTP_ERR_ARG;
     const int64_t total = N * H * W * (C / 4);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == MTP_BF16) hipLaunchKernelGGL((dwconvk_kernel<bf16_t, false>), dim3(blocks_for(total)), dim3(256), 0, s, (const bf16_t*)x, w, bias, (bf16_t*)y, (float*)nullptr, 0, (int)H, (int)W, (int)C, k, total);
-    else if (dtype == MTP_F32) hipLaunchKernelGGL((dwconvk_kernel<float, false>), dim3(blocks_for(total)), dim3(256), 0, s, (const float*)x, w, bias, (float*)y, (float*)nullptr, 0, (int)H, (int)W, (int)C, k, total);
-    else return MTP_ERR_UNSUPPORTED;
-    return mtp_launch_status();
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        dwconvk_kernel<T, false><<<blocks_exact(total), kThreads, 0, (hipStream_t)stream>>>((const T*)x, w, bias, (T*)y, (float*)nullptr, 0, (int)H, (int)W, (int)C, k, total);
+    });
 }
 extern "C" int mtp_dwconv_bwd_dx(const void* dy, int dtype, const float* w, float* dx, int accumulate, int64_t N, int64_t H, int64_t W, int64_t C, int k, mtp_stream_t stream) {
-    if (!dy || !w || !dx || N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 4) || k < 1 || !(k & 1) || k > 15) return MTP_ERR_ARG;
+    if (!dwconvk_args_ok(dy, w, dx, N, H, W, C, k)) return MTP_ERR_ARG;
     const int64_t total = N * H * W * (C / 4);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == MTP_BF16) hipLaunchKernelGGL((dwconvk_kernel<bf16_t, true>), dim3(blocks_for(total)), dim3(256), 0, s, (const bf16_t*)dy, w, (const float*)nullptr, (bf16_t*)nullptr, dx, accumulate, (int)H, (int)W, (int)C, k, total);
-    else if (dtype == MTP_F32) hipLaunchKernelGGL((dwconvk_kernel<float, true>), dim3(blocks_for(total)), dim3(256), 0, s, (const float*)dy, w, (const float*)nullptr, (float*)nullptr, dx, accumulate, (int)H, (int)W, (int)C, k, total);
-    else return MTP_ERR_UNSUPPORTED;
-    return mtp_launch_status();
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        dwconvk_kernel<T, true><<<blocks_exact(total), kThreads, 0, (hipStream_t)stream>>>((const T*)dy, w, (const float*)nullptr, (T*)nullptr, dx, accumulate, (int)H, (int)W, (int)C, k, total);
+    });
 }
 extern "C" int mtp_dwconv_bwd_dw(const void* dy, const void* x, int dtype, float* dw, float* db, int64_t N, int64_t H, int64_t W, int64_t C, int k, mtp_stream_t stream) {
-    if (!dy || !x || !dw || N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 4) || k < 1 || !(k & 1) || k > 15) return MTP_ERR_ARG;
+    if (!dwconvk_args_ok(dy, x, dw, N, H, W, C, k)) return MTP_ERR_ARG;
     const int64_t pixels = N * H * W;
     int64_t rb = (pixels + 511) / 512;
     rb = rb < 256 ? rb : 256;
     const int64_t rpb = ((pixels + rb - 1) / rb + 3) / 4 * 4;
-    const dim3 grid((unsigned)((C / 4 + 63) / 64), (unsigned)((pixels + rpb - 1) / rpb), (unsigned)(k * k)), block(256);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == MTP_BF16) hipLaunchKernelGGL((dwconvk_dw_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)dy, (const bf16_t*)x, dw, db, (int)H, (int)W, (int)C, k, pixels, rpb);
-    else if (dtype == MTP_F32) hipLaunchKernelGGL((dwconvk_dw_kernel<float>), grid, block, 0, s, (const float*)dy, (const float*)x, dw, db, (int)H, (int)W, (int)C, k, pixels, rpb);
-    else return MTP_ERR_UNSUPPORTED;
-    return mtp_launch_status();
+    const dim3 grid((unsigned)((C / 4 + 63) / 64), (unsigned)((pixels + rpb - 1) / rpb), (unsigned)(k * k));
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        dwconvk_dw_kernel<T><<<grid, kThreads, 0, (hipStream_t)stream>>>((const T*)dy, (const T*)x, dw, db, (int)H, (int)W, (int)C, k, pixels, rpb);
+    });
 }
 
 /* ---- center_feature_scale (InternImage-H/G; ops_dcnv3/modules/dcnv3.py:209-215): out (rows, G * GC) = y (1 - s) + xp s with s = sigmoid(logits[row][group]) (logits:
@@ -911,19 +900,17 @@ extern "C" int mtp_dwconv_bwd_dw(const void* dy, const void* x, int dtype, float
 extern "C" int mtp_center_feature_scale_fwd(const void* y, const void* xp, const void* logits, int64_t ld, void* out, int dtype, int64_t rows, int64_t G, int64_t GC, mtp_stream_t stream) {
     if (!y || !xp || !logits || !out || rows <= 0 || G <= 0 || GC <= 0 || (GC % 4) || ld < G) return MTP_ERR_ARG;
     const int64_t total = rows * G;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == MTP_BF16) hipLaunchKernelGGL((cfs_kernel<bf16_t, false>), dim3(blocks_for(total)), dim3(256), 0, s, (const bf16_t*)nullptr, (const bf16_t*)y, (const bf16_t*)xp, (const bf16_t*)logits, ld, (bf16_t*)out, (float*)nullptr, (bf16_t*)nullptr, (int)G, (int)GC, total);
-    else if (dtype == MTP_F32) hipLaunchKernelGGL((cfs_kernel<float, false>), dim3(blocks_for(total)), dim3(256), 0, s, (const float*)nullptr, (const float*)y, (const float*)xp, (const float*)logits, ld, (float*)out, (float*)nullptr, (float*)nullptr, (int)G, (int)GC, total);
-    else return MTP_ERR_UNSUPPORTED;
-    return mtp_launch_status();
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        cfs_kernel<T, false><<<blocks_exact(total), kThreads, 0, (hipStream_t)stream>>>((const T*)nullptr, (const T*)y, (const T*)xp, (const T*)logits, ld, (T*)out, (float*)nullptr, (T*)nullptr, (int)G, (int)GC, total);
+    });
 }
 extern "C" int mtp_center_feature_scale_bwd(const void* dout, const void* y, const void* xp, const void* logits, int64_t ld, void* dy, float* dxp, void* dlogits, int dtype, int64_t rows,
                                             int64_t G, int64_t GC, mtp_stream_t stream) {
     if (!dout || !y || !xp || !logits || !dy || !dxp || !dlogits || rows <= 0 || G <= 0 || GC <= 0 || (GC % 4) || ld < G) return MTP_ERR_ARG;
     const int64_t total = rows * G;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == MTP_BF16) hipLaunchKernelGGL((cfs_kernel<bf16_t, true>), dim3(blocks_for(total)), dim3(256), 0, s, (const bf16_t*)dout, (const bf16_t*)y, (const bf16_t*)xp, (const bf16_t*)logits, ld, (bf16_t*)dy, dxp, (bf16_t*)dlogits, (int)G, (int)GC, total);
-    else if (dtype == MTP_F32) hipLaunchKernelGGL((cfs_kernel<float, true>), dim3(blocks_for(total)), dim3(256), 0, s, (const float*)dout, (const float*)y, (const float*)xp, (const float*)logits, ld, (float*)dy, dxp, (float*)dlogits, (int)G, (int)GC, total);
-    else return MTP_ERR_UNSUPPORTED;
-    return mtp_launch_status();
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        cfs_kernel<T, true><<<blocks_exact(total), kThreads, 0, (hipStream_t)stream>>>((const T*)dout, (const T*)y, (const T*)xp, (const T*)logits, ld, (T*)dy, dxp, (T*)dlogits, (int)G, (int)GC, total);
+    });
 }

@@ -841,13 +841,13 @@ int launch_fwd(const void* input, const void* offset, const void* mask, void* ou
     const int64_t items = (int64_t)g.N * g.Ho * g.Wo * g.G;
     if (fam == MTP_DCNV3_FWD9) {
         const int64_t total = items * (g.GC / 8);
-        hipLaunchKernelGGL((dcnv3_fwd9_kernel<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const T*)input, (const T*)offset, (const T*)mask, (T*)output, g, total);
+        dcnv3_fwd9_kernel<T><<<blocks_exact(total), kThreads, 0, s>>>((const T*)input, (const T*)offset, (const T*)mask, (T*)output, g, total);
     } else if (fam == MTP_DCNV3_FWD_VEC8) {
         const int64_t total = items * (g.GC / 8);
-        hipLaunchKernelGGL((dcnv3_fwd_kernel<T, 8>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const T*)input, (const T*)offset, (const T*)mask, (T*)output, g, total);
+        dcnv3_fwd_kernel<T, 8><<<blocks_exact(total), kThreads, 0, s>>>((const T*)input, (const T*)offset, (const T*)mask, (T*)output, g, total);
     } else {
         const int64_t total = items * g.GC;
-        hipLaunchKernelGGL((dcnv3_fwd_kernel<T, 1>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const T*)input, (const T*)offset, (const T*)mask, (T*)output, g, total);
+        dcnv3_fwd_kernel<T, 1><<<blocks_exact(total), kThreads, 0, s>>>((const T*)input, (const T*)offset, (const T*)mask, (T*)output, g, total);
     }
     return mtp_launch_status();
 }
@@ -860,10 +860,10 @@ int launch_bwd_gather(const void* input, const void* offset, const void* mask, c
     static unsigned long long optin = 0;     // (one per instantiation of this launcher: per kernel; the bit set inside is per device)
     if (const int e = mtp_optin_lds(OS3 ? (const void*)dcnv3_bwd_input3x3_kernel<T, (OS3 ? OS3 : 1)> : (const void*)dcnv3_bwd_input_kernel<T, R>, LDS, optin)) return e;
     if constexpr (OS3 != 0)
-        hipLaunchKernelGGL((dcnv3_bwd_input3x3_kernel<T, (OS3 ? OS3 : 1)>), dim3((unsigned)blocks), dim3(256), LDS, s, (const T*)offset, (const T*)mask, (const T*)grad_output, grad_input, g, tiles_x, tiles_y);
+        dcnv3_bwd_input3x3_kernel<T, (OS3 ? OS3 : 1)><<<(unsigned)blocks, kThreads, LDS, s>>>((const T*)offset, (const T*)mask, (const T*)grad_output, grad_input, g, tiles_x, tiles_y);
     else
-        hipLaunchKernelGGL((dcnv3_bwd_input_kernel<T, R>), dim3((unsigned)blocks), dim3(256), LDS, s, (const T*)offset, (const T*)mask, (const T*)grad_output, grad_input, g, tiles_x, tiles_y);
-    hipLaunchKernelGGL((dcnv3_bwd_om_kernel<T, (OS3 ? 2 : 1)>), dim3((unsigned)((2 * items + 255) / 256)), dim3(256), 0, s, (const T*)input, (const T*)offset, (const T*)mask, (const T*)grad_output,
+        dcnv3_bwd_input_kernel<T, R><<<(unsigned)blocks, kThreads, LDS, s>>>((const T*)offset, (const T*)mask, (const T*)grad_output, grad_input, g, tiles_x, tiles_y);
+    dcnv3_bwd_om_kernel<T, (OS3 ? 2 : 1)><<<blocks_exact(2 * items), kThreads, 0, s>>>((const T*)input, (const T*)offset, (const T*)mask, (const T*)grad_output,
                        grad_input, grad_offset, grad_mask, g, items, R);
     return mtp_launch_status();
 }
@@ -891,10 +891,10 @@ int launch_bwd(const void* input, const void* offset, const void* mask, const vo
         e = hipMemsetAsync(grad_offset, 0, sizeof(float) * (size_t)items * 2 * g.P, s);
         if (e == hipSuccess) e = hipMemsetAsync(grad_mask, 0, sizeof(float) * (size_t)items * g.P, s);
         if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((dcnv3_bwd_kernel<T, false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const T*)input, (const T*)offset, (const T*)mask, (const T*)grad_output,
+        dcnv3_bwd_kernel<T, false><<<blocks_exact(total), kThreads, 0, s>>>((const T*)input, (const T*)offset, (const T*)mask, (const T*)grad_output,
                            grad_input, grad_offset, grad_mask, g, total);
     } else {
-        hipLaunchKernelGGL((dcnv3_bwd_kernel<T, true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const T*)input, (const T*)offset, (const T*)mask, (const T*)grad_output,
+        dcnv3_bwd_kernel<T, true><<<blocks_exact(total), kThreads, 0, s>>>((const T*)input, (const T*)offset, (const T*)mask, (const T*)grad_output,
                            grad_input, grad_offset, grad_mask, g, total);
     }
     return mtp_launch_status();
@@ -908,7 +908,7 @@ int dcn_decide(const void* input, const void* offset, const void* mask, const vo
     const int rc = make_geom(geom, g);
     if (rc) return rc == MTP_ERR_UNSUPPORTED ? (int)MTP_DCNV3_KERNEL_NONE : rc;
     MTP_CHECK_ARG(input && offset && mask && out && (!backward || (grad_input && grad_offset && grad_mask)));
-    MTP_CHECK_ARG(dtype == MTP_F32 || dtype == MTP_BF16 || (f64 && dtype == MTP_F64));
+    MTP_CHECK_ARG(dt_ok(dtype) || (f64 && dtype == MTP_F64));
     if (dtype == MTP_F64 && !backward) return MTP_DCNV3_F64;      // (one lane per element, 64-bit indices: no size limit)
     if ((int64_t)g.N * g.Ho * g.Wo * g.G * g.GC >= ((int64_t)1 << 32) - 256) return MTP_DCNV3_KERNEL_NONE;   // one lane per element at most
     if (dtype == MTP_F64) return MTP_DCNV3_F64;
@@ -934,7 +934,7 @@ extern "C" int mtp_dcnv3_fwd(const void* input, const void* offset, const void* 
     hipStream_t s = (hipStream_t)stream;
     if (fam == MTP_DCNV3_F64) {
         const int64_t total = (int64_t)g.N * g.Ho * g.Wo * g.G * g.GC;
-        hipLaunchKernelGGL(dcnv3_f64_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const double*)input, (const double*)offset,
+        dcnv3_f64_kernel<false><<<blocks_exact(total), kThreads, 0, s>>>((const double*)input, (const double*)offset,
                            (const double*)mask, (const double*)nullptr, (double*)output, (double*)nullptr, (double*)nullptr, (double*)nullptr, g, total);
         return mtp_launch_status();
     }
@@ -968,7 +968,7 @@ extern "C" int mtp_dcnv3_bwd(const void* input, const void* offset, const void* 
         if (e == hipSuccess) e = hipMemsetAsync(grad_offset, 0, sizeof(double) * (size_t)items * 2 * g.P, s);
         if (e == hipSuccess) e = hipMemsetAsync(grad_mask, 0, sizeof(double) * (size_t)items * g.P, s);
         if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(dcnv3_f64_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const double*)input, (const double*)offset, (const double*)mask,
+        dcnv3_f64_kernel<true><<<blocks_exact(total), kThreads, 0, s>>>((const double*)input, (const double*)offset, (const double*)mask,
                            (const double*)grad_output, (double*)nullptr, reinterpret_cast<double*>(grad_input), reinterpret_cast<double*>(grad_offset),
                            reinterpret_cast<double*>(grad_mask), g, total);
         return mtp_launch_status();

@@ -7,32 +7,6 @@
 
 namespace {
 
-constexpr int kThreads = 256;
-
-template <typename T>
-__device__ __forceinline__ float ld1(const void* p, int64_t i) { return Elem<T>::load(reinterpret_cast<const T*>(p) + i); }
-template <typename T>
-__device__ __forceinline__ float4 ld4(const void* p, int64_t i) { return load4(reinterpret_cast<const T*>(p) + i); }
-template <typename T>
-__device__ __forceinline__ void st4(void* p, int64_t i, float4 v) { store4(reinterpret_cast<T*>(p) + i, v); }
-
-__device__ __forceinline__ float4 f4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 f4scale(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
-__device__ __forceinline__ float4 f4fma(float4 a, float s, float4 acc) {
-    return make_float4(fmaf(a.x, s, acc.x), fmaf(a.y, s, acc.y), fmaf(a.z, s, acc.z), fmaf(a.w, s, acc.w));
-}
-
-// dtype dispatch of a kernel template over (T_in, T_out)
-#define MTP_DISPATCH2(DT_A, DT_B, ...)                                                                        \
-    do {                                                                                                      \
-        if ((DT_A) == MTP_F32 && (DT_B) == MTP_F32) { using TA = float; using TB = float; __VA_ARGS__; }      \
-        else if ((DT_A) == MTP_F32) { using TA = float; using TB = bf16_t; __VA_ARGS__; }                     \
-        else if ((DT_B) == MTP_F32) { using TA = bf16_t; using TB = float; __VA_ARGS__; }                     \
-        else { using TA = bf16_t; using TB = bf16_t; __VA_ARGS__; }                                           \
-    } while (0)
-
-inline bool dt_ok(int dt) { return dt == MTP_F32 || dt == MTP_BF16; }
-
 // ---------------------------------------------------------------------------------------------------------------- BatchNorm
 // rows are split into `nblk` contiguous chunks (a function of `rows` alone, so the summation order never changes); a workgroup of 4 waves
 // takes one chunk and 256 channels (4 per lane), the waves stride its rows and are combined in LDS in wave order.
@@ -403,8 +377,6 @@ __global__ void __launch_bounds__(kThreads) resize_bwd1_kernel(const float* dy, 
     dx[pix * lddx + k] = acc;
 }
 
-inline unsigned grid1(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
 }  // namespace
 
 // ======================================================================================================================== C ABI
@@ -417,7 +389,7 @@ extern "C" int mtp_bn_stats(const void* x, int dtype, int64_t ldx, const float* 
     const dim3 grid((unsigned)nb, (unsigned)((C / 4 + 63) / 64));
     if (dtype == MTP_F32) bn_stats_kernel<float><<<grid, kThreads, 0, (hipStream_t)stream>>>(x, ldx, center, part, rows, C, chunk);
     else bn_stats_kernel<bf16_t><<<grid, kThreads, 0, (hipStream_t)stream>>>(x, ldx, center, part, rows, C, chunk);
-    col_sums_kernel<<<grid1(2 * C), kThreads, 0, (hipStream_t)stream>>>(part, nb, 2 * C, sums);
+    col_sums_kernel<<<blocks_exact(2 * C), kThreads, 0, (hipStream_t)stream>>>(part, nb, 2 * C, sums);
     return mtp_launch_status();
 }
 
@@ -425,7 +397,7 @@ extern "C" int mtp_bn_finalize(const float* sums, const float* center, double co
                                int64_t C, mtp_stream_t stream) {
     MTP_CHECK_ARG(mean && rstd && C > 0);
     MTP_CHECK_ARG(sums ? count > 0.0 && ((running_mean == nullptr) == (running_var == nullptr)) : (running_mean && running_var));
-    bn_finalize_kernel<<<grid1(C), kThreads, 0, (hipStream_t)stream>>>(sums, center, count, running_mean, running_var, momentum, eps, mean, rstd, C);
+    bn_finalize_kernel<<<blocks_exact(C), kThreads, 0, (hipStream_t)stream>>>(sums, center, count, running_mean, running_var, momentum, eps, mean, rstd, C);
     return mtp_launch_status();
 }
 
@@ -434,7 +406,7 @@ extern "C" int mtp_bn_apply(const void* x, int x_dtype, int64_t ldx, const float
     MTP_CHECK_ARG(x && mean && rstd && gamma && beta && y && rows > 0 && C > 0 && (C % 4) == 0 && dt_ok(x_dtype) && dt_ok(y_dtype));
     MTP_CHECK_ARG(ldx >= C && ldy >= C && (ldx % 4) == 0 && (ldy % 4) == 0);
     MTP_DISPATCH2(x_dtype, y_dtype,
-                  bn_apply_kernel<TA, TB><<<grid1(rows * (C / 4)), kThreads, 0, (hipStream_t)stream>>>(x, ldx, mean, rstd, gamma, beta, relu, y, ldy, rows, C));
+                  bn_apply_kernel<TA, TB><<<blocks_exact(rows * (C / 4)), kThreads, 0, (hipStream_t)stream>>>(x, ldx, mean, rstd, gamma, beta, relu, y, ldy, rows, C));
     return mtp_launch_status();
 }
 
@@ -446,7 +418,7 @@ extern "C" int mtp_bn_bwd_stats(const void* dy, int dy_dtype, int64_t lddy, cons
     const dim3 grid((unsigned)nb, (unsigned)((C / 4 + 63) / 64));
     MTP_DISPATCH2(x_dtype, dy_dtype,
                   bn_bwd_stats_kernel<TA, TB><<<grid, kThreads, 0, (hipStream_t)stream>>>(dy, lddy, x, ldx, mean, rstd, gamma, beta, relu, part, rows, C, chunk));
-    col_sums_kernel<<<grid1(2 * C), kThreads, 0, (hipStream_t)stream>>>(part, nb, 2 * C, sums);
+    col_sums_kernel<<<blocks_exact(2 * C), kThreads, 0, (hipStream_t)stream>>>(part, nb, 2 * C, sums);
     return mtp_launch_status();
 }
 
@@ -457,7 +429,7 @@ extern "C" int mtp_bn_bwd_dx(const void* dy, int dy_dtype, int64_t lddy, const v
     MTP_CHECK_ARG(dt_ok(dy_dtype) && dt_ok(x_dtype) && dt_ok(dx_dtype) && (!sums || count > 0.0));
     MTP_CHECK_ARG(ldx >= C && lddy >= C && lddx >= C && (ldx % 4) == 0 && (lddy % 4) == 0 && (lddx % 4) == 0);
     const float inv = sums ? (float)(1.0 / count) : 0.0f;
-    const unsigned g = grid1(rows * (C / 4));
+    const unsigned g = blocks_exact(rows * (C / 4));
     hipStream_t s = (hipStream_t)stream;
     // (x, dy) dtypes x dx dtype
     if (dx_dtype == MTP_F32) {
@@ -473,7 +445,7 @@ extern "C" int mtp_resize_bilinear_fwd(const void* x, int x_dtype, int64_t ldx, 
     MTP_CHECK_ARG(x && y && N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0 && (C % 4) == 0 && dt_ok(x_dtype) && dt_ok(y_dtype));
     MTP_CHECK_ARG(ldx >= C && ldy >= C && (ldx % 4) == 0 && (ldy % 4) == 0 && Hi < INT32_MAX && Wi < INT32_MAX && Ho < INT32_MAX && Wo < INT32_MAX);
     MTP_DISPATCH2(x_dtype, y_dtype,
-                  resize_fwd_kernel<TA, TB><<<grid1(N * Ho * Wo * (C / 4)), kThreads, 0, (hipStream_t)stream>>>(x, ldx, y, ldy, N, (int)Hi, (int)Wi, (int)Ho,
+                  resize_fwd_kernel<TA, TB><<<blocks_exact(N * Ho * Wo * (C / 4)), kThreads, 0, (hipStream_t)stream>>>(x, ldx, y, ldy, N, (int)Hi, (int)Wi, (int)Ho,
                                                                                                               (int)Wo, C, accumulate));
     return mtp_launch_status();
 }
@@ -482,7 +454,7 @@ extern "C" int mtp_resize_bilinear_bwd(const void* dy, int dy_dtype, int64_t ldd
                                        int64_t Wo, int64_t C, int accumulate, mtp_stream_t stream) {
     MTP_CHECK_ARG(dy && dx && N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0 && (C % 4) == 0 && dt_ok(dy_dtype));
     MTP_CHECK_ARG(lddx >= C && lddy >= C && (lddx % 4) == 0 && (lddy % 4) == 0 && Hi < INT32_MAX && Wi < INT32_MAX && Ho < INT32_MAX && Wo < INT32_MAX);
-    const unsigned g = grid1(N * Hi * Wi * (C / 4));
+    const unsigned g = blocks_exact(N * Hi * Wi * (C / 4));
     if (dy_dtype == MTP_F32)
         resize_bwd_kernel<float><<<g, kThreads, 0, (hipStream_t)stream>>>(dy, lddy, dx, lddx, N, (int)Hi, (int)Wi, (int)Ho, (int)Wo, C, accumulate);
     else
@@ -495,7 +467,7 @@ extern "C" int mtp_adaptive_avg_pool_fwd(const void* x, int x_dtype, int64_t ldx
     MTP_CHECK_ARG(x && y && N > 0 && H > 0 && W > 0 && C > 0 && (C % 4) == 0 && S > 0 && S <= 64 && ldx >= C && (ldx % 4) == 0);
     MTP_CHECK_ARG(dt_ok(x_dtype) && dt_ok(y_dtype) && H < INT32_MAX && W < INT32_MAX);
     MTP_DISPATCH2(x_dtype, y_dtype,
-                  pool_fwd_kernel<TA, TB><<<grid1(N * S * S * (C / 4)), kThreads, 0, (hipStream_t)stream>>>(x, ldx, y, N, (int)H, (int)W, C, (int)S));
+                  pool_fwd_kernel<TA, TB><<<blocks_exact(N * S * S * (C / 4)), kThreads, 0, (hipStream_t)stream>>>(x, ldx, y, N, (int)H, (int)W, C, (int)S));
     return mtp_launch_status();
 }
 
@@ -503,7 +475,7 @@ extern "C" int mtp_adaptive_avg_pool_bwd(const void* dy, int dy_dtype, float* dx
                                          int accumulate, mtp_stream_t stream) {
     MTP_CHECK_ARG(dy && dx && N > 0 && H > 0 && W > 0 && C > 0 && (C % 4) == 0 && S > 0 && S <= 64 && lddx >= C && (lddx % 4) == 0 && dt_ok(dy_dtype));
     MTP_CHECK_ARG(H < INT32_MAX && W < INT32_MAX);
-    const unsigned g = grid1(N * H * W * (C / 4));
+    const unsigned g = blocks_exact(N * H * W * (C / 4));
     if (dy_dtype == MTP_F32) pool_bwd_kernel<float><<<g, kThreads, 0, (hipStream_t)stream>>>(dy, dx, lddx, N, (int)H, (int)W, C, (int)S, accumulate);
     else pool_bwd_kernel<bf16_t><<<g, kThreads, 0, (hipStream_t)stream>>>(dy, dx, lddx, N, (int)H, (int)W, C, (int)S, accumulate);
     return mtp_launch_status();
@@ -514,7 +486,7 @@ extern "C" int mtp_channel_scale(const void* x, int x_dtype, int64_t ldx, const 
     MTP_CHECK_ARG(x && mask && y && rows > 0 && C > 0 && (C % 4) == 0 && rows_per_sample > 0 && dt_ok(x_dtype) && dt_ok(y_dtype));
     MTP_CHECK_ARG(ldx >= C && ldy >= C && (ldx % 4) == 0 && (ldy % 4) == 0);
     MTP_DISPATCH2(x_dtype, y_dtype,
-                  channel_scale_kernel<TA, TB><<<grid1(rows * (C / 4)), kThreads, 0, (hipStream_t)stream>>>(x, ldx, mask, rows_per_sample, y, ldy, rows, C));
+                  channel_scale_kernel<TA, TB><<<blocks_exact(rows * (C / 4)), kThreads, 0, (hipStream_t)stream>>>(x, ldx, mask, rows_per_sample, y, ldy, rows, C));
     return mtp_launch_status();
 }
 
@@ -545,6 +517,6 @@ extern "C" int mtp_seg_ce(const void* logits, int dtype, int64_t ld, int64_t N, 
     else
         seg_ce_kernel<bf16_t, int64_t><<<g, kThreads, 0, s>>>(logits, ld, (const int64_t*)labels, N, (int)h, (int)w, (int)K, (int)H, (int)W, ignore_index, scale, dhr, part);
     sum_scale_kernel<<<1, kThreads, 0, s>>>(part, nb, scale, loss);
-    resize_bwd1_kernel<float><<<grid1(N * h * w * K), kThreads, 0, s>>>(dhr, (int)K, dlogits, ldd, N, (int)h, (int)w, (int)H, (int)W);
+    resize_bwd1_kernel<float><<<blocks_exact(N * h * w * K), kThreads, 0, s>>>(dhr, (int)K, dlogits, ldd, N, (int)h, (int)w, (int)H, (int)W);
     return mtp_launch_status();
 }

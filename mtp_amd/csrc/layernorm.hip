@@ -457,11 +457,9 @@ int ln_grid(int64_t rows) {
 template <typename Tx, typename Ty>
 int launch_ln_fwd(const void* x, const float* g, const float* b, void* y, float* mean, float* rstd, int64_t rows, int64_t C, float eps, int gelu, hipStream_t s) {
     dim3 grid(ln_grid(rows)), block(LN_THREADS);
-#define MTP_CALL(MV_)                                                                                                                                        \
-    if (gelu)                                                                                                                                                \
-        hipLaunchKernelGGL((ln_fwd_kernel<Tx, Ty, true, MV_>), grid, block, 0, s, (const Tx*)x, g, b, (Ty*)y, mean, rstd, rows, (int)C, eps);                \
-    else                                                                                                                                                     \
-        hipLaunchKernelGGL((ln_fwd_kernel<Tx, Ty, false, MV_>), grid, block, 0, s, (const Tx*)x, g, b, (Ty*)y, mean, rstd, rows, (int)C, eps)
+#define MTP_CALL(MV_)                                                                                                             \
+    if (gelu) ln_fwd_kernel<Tx, Ty, true, MV_><<<grid, block, 0, s>>>((const Tx*)x, g, b, (Ty*)y, mean, rstd, rows, (int)C, eps); \
+    else ln_fwd_kernel<Tx, Ty, false, MV_><<<grid, block, 0, s>>>((const Tx*)x, g, b, (Ty*)y, mean, rstd, rows, (int)C, eps)
     MTP_LN_MV(C, MTP_CALL);
 #undef MTP_CALL
     return mtp_launch_status();
@@ -472,13 +470,15 @@ int launch_ln_bwd(const void* dy, const void* x, const float* mean, const float*
                   const float* dres, const float* extra, void* dx, void* dx_copy, const float* copy_scale, int64_t rps,
                   float* dgp, float* dbp, int64_t part_ld, int64_t rows, int64_t C, hipStream_t s, const float* win_add = nullptr, LnWin wg = LnWin{1, 1, 0, 0, 1, 1}) {
     dim3 grid((unsigned)mtp_layernorm_bwd_partial_rows(rows)), block(LN_THREADS);
-#define MTP_CALL(MV_)                                                                                                                                        \
-    if (gelu)                                                                                                                                                \
-        hipLaunchKernelGGL((ln_bwd_kernel<Tact, Tx, Tdx, true, MV_>), grid, block, 0, s, (const Tact*)dy, (const Tx*)x, mean, rstd, gamma, beta, dres, extra, \
-                           (Tdx*)dx, (Tact*)dx_copy, copy_scale, (int)(rps > 0 ? rps : 1), dgp, dbp, part_ld, rows, (int)C, win_add, wg);                    \
-    else                                                                                                                                                     \
-        hipLaunchKernelGGL((ln_bwd_kernel<Tact, Tx, Tdx, false, MV_>), grid, block, 0, s, (const Tact*)dy, (const Tx*)x, mean, rstd, gamma, beta, dres, extra, \
-                           (Tdx*)dx, (Tact*)dx_copy, copy_scale, (int)(rps > 0 ? rps : 1), dgp, dbp, part_ld, rows, (int)C, win_add, wg)
+#define MTP_CALL(MV_)                                                                                                                             \
+    if (gelu)                                                                                                                                     \
+        ln_bwd_kernel<Tact, Tx, Tdx, true, MV_><<<grid, block, 0, s>>>((const Tact*)dy, (const Tx*)x, mean, rstd, gamma, beta, dres, extra,       \
+                                                                       (Tdx*)dx, (Tact*)dx_copy, copy_scale, (int)(rps > 0 ? rps : 1), dgp, dbp,  \
+                                                                       part_ld, rows, (int)C, win_add, wg);                                       \
+    else                                                                                                                                          \
+        ln_bwd_kernel<Tact, Tx, Tdx, false, MV_><<<grid, block, 0, s>>>((const Tact*)dy, (const Tx*)x, mean, rstd, gamma, beta, dres, extra,      \
+                                                                        (Tdx*)dx, (Tact*)dx_copy, copy_scale, (int)(rps > 0 ? rps : 1), dgp, dbp, \
+                                                                        part_ld, rows, (int)C, win_add, wg)
     MTP_LN_MV(C, MTP_CALL);
 #undef MTP_CALL
     return mtp_launch_status();
@@ -498,21 +498,20 @@ extern "C" int mtp_layernorm_fwd(const void* x, int x_dtype, const float* gamma,
 }
 
 template <typename Th>
-static int launch_ln_res(bool fwd, const void* a0, const void* h, const float* mean_c, float* mean, const float* rstd_c, float* rstd, const float* gamma, const float* beta,
+static void launch_ln_res(bool fwd, const void* a0, const void* h, const float* mean_c, float* mean, const float* rstd_c, float* rstd, const float* gamma, const float* beta,
                          const float* x, const float* ls, const float* ss, int rps, float* out, void* oact, void* dh, float* part, int64_t rows, int64_t C, float eps,
                          hipStream_t s) {
     if (fwd) {
         const dim3 grid(ln_grid(rows)), block(LN_THREADS);
-#define MTP_CALL(MV_) hipLaunchKernelGGL((ln_res_fwd_kernel<Th, MV_>), grid, block, 0, s, (const Th*)h, gamma, beta, x, ls, ss, rps, out, (Th*)oact, mean, rstd, rows, (int)C, eps)
+#define MTP_CALL(MV_) ln_res_fwd_kernel<Th, MV_><<<grid, block, 0, s>>>((const Th*)h, gamma, beta, x, ls, ss, rps, out, (Th*)oact, mean, rstd, rows, (int)C, eps)
         MTP_LN_MV(C, MTP_CALL);
 #undef MTP_CALL
     } else {
         const dim3 grid((unsigned)mtp_layernorm_bwd_partial_rows(rows)), block(LN_THREADS);
-#define MTP_CALL(MV_) hipLaunchKernelGGL((ln_res_bwd_kernel<Th, MV_>), grid, block, 0, s, (const float*)a0, (const Th*)h, mean_c, rstd_c, gamma, beta, ls, ss, rps, (Th*)dh, part, rows, (int)C)
+#define MTP_CALL(MV_) ln_res_bwd_kernel<Th, MV_><<<grid, block, 0, s>>>((const float*)a0, (const Th*)h, mean_c, rstd_c, gamma, beta, ls, ss, rps, (Th*)dh, part, rows, (int)C)
         MTP_LN_MV(C, MTP_CALL);
 #undef MTP_CALL
     }
-    return mtp_launch_status();
 }
 
 extern "C" int mtp_layernorm_residual_fwd(const void* h, int dtype, const float* gamma, const float* beta, const float* x, const float* layer_scale,
@@ -521,9 +520,9 @@ extern "C" int mtp_layernorm_residual_fwd(const void* h, int dtype, const float*
     if (!h || !gamma || !beta || !x || !layer_scale || !out || !mean || !rstd || rows <= 0 || rows > INT32_MAX || C <= 0 || (C % 4) || C > 256 * MAXV) return MTP_ERR_ARG;
     if (sample_scale && rows_per_sample <= 0) return MTP_ERR_ARG;
     const int rps = (int)(rows_per_sample > 0 ? rows_per_sample : 1);
-    if (dtype == MTP_BF16) return launch_ln_res<bf16_t>(true, nullptr, h, nullptr, mean, nullptr, rstd, gamma, beta, x, layer_scale, sample_scale, rps, out, out_act, nullptr, nullptr, rows, C, eps, (hipStream_t)stream);
-    if (dtype == MTP_F32) return launch_ln_res<float>(true, nullptr, h, nullptr, mean, nullptr, rstd, gamma, beta, x, layer_scale, sample_scale, rps, out, out_act, nullptr, nullptr, rows, C, eps, (hipStream_t)stream);
-    return MTP_ERR_UNSUPPORTED;
+    return for_act(dtype, [&](auto t) {
+        launch_ln_res<decltype(t)>(true, nullptr, h, nullptr, mean, nullptr, rstd, gamma, beta, x, layer_scale, sample_scale, rps, out, out_act, nullptr, nullptr, rows, C, eps, (hipStream_t)stream);
+    });
 }
 
 extern "C" int mtp_layernorm_residual_bwd(const float* dout, const void* h, int dtype, const float* mean, const float* rstd, const float* gamma, const float* beta,
@@ -532,9 +531,9 @@ extern "C" int mtp_layernorm_residual_bwd(const float* dout, const void* h, int 
     if (!dout || !h || !mean || !rstd || !gamma || !beta || !layer_scale || !dh || !part || rows <= 0 || rows > INT32_MAX || C <= 0 || (C % 4) || C > 256 * MAXV) return MTP_ERR_ARG;
     if (sample_scale && rows_per_sample <= 0) return MTP_ERR_ARG;
     const int rps = (int)(rows_per_sample > 0 ? rows_per_sample : 1);
-    if (dtype == MTP_BF16) return launch_ln_res<bf16_t>(false, dout, h, mean, nullptr, rstd, nullptr, gamma, beta, nullptr, layer_scale, sample_scale, rps, nullptr, nullptr, dh, part, rows, C, 0.f, (hipStream_t)stream);
-    if (dtype == MTP_F32) return launch_ln_res<float>(false, dout, h, mean, nullptr, rstd, nullptr, gamma, beta, nullptr, layer_scale, sample_scale, rps, nullptr, nullptr, dh, part, rows, C, 0.f, (hipStream_t)stream);
-    return MTP_ERR_UNSUPPORTED;
+    return for_act(dtype, [&](auto t) {
+        launch_ln_res<decltype(t)>(false, dout, h, mean, nullptr, rstd, nullptr, gamma, beta, nullptr, layer_scale, sample_scale, rps, nullptr, nullptr, dh, part, rows, C, 0.f, (hipStream_t)stream);
+    });
 }
 
 extern "C" int64_t mtp_layernorm_bwd_partial_rows(int64_t rows) {
@@ -600,7 +599,7 @@ extern "C" int mtp_reduce_rows_f32(const float* part, int64_t ld, float* out, in
     if (splits > rows) splits = rows;
     const int64_t rpb = (rows + splits - 1) / splits;
     splits = (rows + rpb - 1) / rpb;
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3((unsigned)col_blocks, (unsigned)splits), dim3(256), 0, s, part, ld, out, rows, C, rpb);
+    reduce_rows_kernel<<<dim3((unsigned)col_blocks, (unsigned)splits), kThreads, 0, s>>>(part, ld, out, rows, C, rpb);
     return mtp_launch_status();
 }
 
@@ -628,7 +627,7 @@ extern "C" int mtp_reduce_rows_batched_f32(const float* const* parts, float* con
     if (splits < 1) splits = 1;
     const int64_t rpb = (rows + splits - 1) / splits;
     splits = (rows + rpb - 1) / rpb;
-    hipLaunchKernelGGL(reduce_rows_batched_kernel, dim3((unsigned)col_blocks, (unsigned)splits, (unsigned)n), dim3(256), 0, s, t, ld, rows, C, rpb);
+    reduce_rows_batched_kernel<<<dim3((unsigned)col_blocks, (unsigned)splits, (unsigned)n), kThreads, 0, s>>>(t, ld, rows, C, rpb);
     return mtp_launch_status();
 }
 
@@ -652,7 +651,7 @@ extern "C" int mtp_reduce_rows_t_batched_f32(const float* const* parts, float* c
     if (splits > rows) splits = rows;
     const int64_t rpb = (rows + splits - 1) / splits;
     splits = (rows + rpb - 1) / rpb;
-    hipLaunchKernelGGL(reduce_rows_t_batched_kernel, dim3((unsigned)col_blocks, (unsigned)splits, (unsigned)n), dim3(256), 0, s, t, ld, rows, (int)R, (int)C, rpb);
+    reduce_rows_t_batched_kernel<<<dim3((unsigned)col_blocks, (unsigned)splits, (unsigned)n), kThreads, 0, s>>>(t, ld, rows, (int)R, (int)C, rpb);
     return mtp_launch_status();
 }
 
@@ -669,7 +668,7 @@ extern "C" int mtp_reduce_rows_t_f32(const float* part, int64_t ld, float* out, 
     if (splits > (rows + 7) / 8) splits = (rows + 7) / 8;
     const int64_t rpb = (rows + splits - 1) / splits;
     splits = (rows + rpb - 1) / rpb;
-    hipLaunchKernelGGL(reduce_rows_t_kernel, dim3((unsigned)col_blocks, (unsigned)splits), dim3(256), 0, s, part, ld, out, rows, (int)R, (int)C, rpb);
+    reduce_rows_t_kernel<<<dim3((unsigned)col_blocks, (unsigned)splits), kThreads, 0, s>>>(part, ld, out, rows, (int)R, (int)C, rpb);
     return mtp_launch_status();
 }
 
@@ -685,6 +684,7 @@ extern "C" int mtp_colsum_acc(const void* dY, int dtype, int64_t ld, float* out,
 
 static int colsum_impl(const void* dY, int dtype, int64_t ld, float* out, int64_t M, int64_t N, bool zero, mtp_stream_t stream) {
     if (!dY || !out || M <= 0 || N <= 0 || (N % 4) || (ld % 4)) return MTP_ERR_ARG;
+    if (!dt_ok(dtype)) return MTP_ERR_UNSUPPORTED;      // before the memset: a refused call writes nothing
     hipStream_t s = (hipStream_t)stream;
     if (zero) {
         hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * (size_t)N, s);
@@ -696,10 +696,9 @@ static int colsum_impl(const void* dY, int dtype, int64_t ld, float* out, int64_
     int64_t rpb = (M + row_blocks - 1) / row_blocks;
     rpb = (rpb + 3) / 4 * 4;
     row_blocks = (M + rpb - 1) / rpb;
-    dim3 grid((unsigned)col_blocks, (unsigned)row_blocks), block(256);
-    if (dtype == MTP_BF16)
-        hipLaunchKernelGGL((colsum_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)dY, ld, out, M, N, rpb);
-    else
-        hipLaunchKernelGGL((colsum_kernel<float>), grid, block, 0, s, (const float*)dY, ld, out, M, N, rpb);
-    return mtp_launch_status();
+    const dim3 grid((unsigned)col_blocks, (unsigned)row_blocks);
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        colsum_kernel<T><<<grid, kThreads, 0, s>>>((const T*)dY, ld, out, M, N, rpb);
+    });
 }

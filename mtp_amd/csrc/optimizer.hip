@@ -275,27 +275,25 @@ __global__ __launch_bounds__(256) void adamw_images_kernel(const mtp_wimg_desc* 
 static int launch_adamw_flat(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_start, const float* seg_wd, const float* seg_lr, int nseg,
                              const float* hyper, const float* sqnorm, float max_norm, float grad_scale, mtp_stream_t stream) {
     if (!p || !g || !m || !v || n <= 0 || (n % 4) || !seg_start || !seg_wd || nseg <= 0 || !hyper) return MTP_ERR_ARG;
-    const dim3 grid(blocks_for(n / 4, 256, 8192)), block(256);
+    const dim3 grid(blocks_for(n / 4, kThreads, 8192)), block(kThreads);
     if (seg_lr)
-        hipLaunchKernelGGL(adamw_kernel<true>, grid, block, 0, (hipStream_t)stream, p, g, m, v, n, seg_start, seg_wd, seg_lr, nseg, hyper, sqnorm, max_norm, grad_scale);
+        adamw_kernel<true><<<grid, block, 0, (hipStream_t)stream>>>(p, g, m, v, n, seg_start, seg_wd, seg_lr, nseg, hyper, sqnorm, max_norm, grad_scale);
     else
-        hipLaunchKernelGGL(adamw_kernel<false>, grid, block, 0, (hipStream_t)stream, p, g, m, v, n, seg_start, seg_wd, seg_lr, nseg, hyper, sqnorm, max_norm, grad_scale);
+        adamw_kernel<false><<<grid, block, 0, (hipStream_t)stream>>>(p, g, m, v, n, seg_start, seg_wd, seg_lr, nseg, hyper, sqnorm, max_norm, grad_scale);
     return mtp_launch_status();
 }
 
 static int launch_adamw_images(const mtp_wimg_desc* descs_dev, const float* desc_lr, int n, int64_t total_tiles, int act_dtype, float* p_base, const float* g_base,
                                float* m_base, float* v_base, const float* hyper, const float* sqnorm, float max_norm, float grad_scale, mtp_stream_t stream) {
     if (!descs_dev || n <= 0 || total_tiles <= 0 || total_tiles > INT32_MAX || !p_base || !g_base || !m_base || !v_base || !hyper) return MTP_ERR_ARG;
-#define MTP_AW(T, LR)                                                                                                                                        \
-    hipLaunchKernelGGL((adamw_images_kernel<T, LR>), dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, descs_dev, desc_lr, n, p_base, g_base, \
-                       m_base, v_base, hyper, sqnorm, max_norm, grad_scale)
-    if (act_dtype == MTP_BF16) {
-        if (desc_lr) MTP_AW(bf16_t, true); else MTP_AW(bf16_t, false);
-    } else if (act_dtype == MTP_F32) {
-        if (desc_lr) MTP_AW(float, true); else MTP_AW(float, false);
-    } else return MTP_ERR_UNSUPPORTED;
-#undef MTP_AW
-    return mtp_launch_status();
+    return for_act(act_dtype, [&](auto t) {
+        using T = decltype(t);
+        auto launch = [&](auto kernel) {
+            kernel<<<(unsigned)total_tiles, kThreads, 0, (hipStream_t)stream>>>(descs_dev, desc_lr, n, p_base, g_base, m_base, v_base, hyper, sqnorm, max_norm, grad_scale);
+        };
+        if (desc_lr) launch(adamw_images_kernel<T, true>);
+        else launch(adamw_images_kernel<T, false>);
+    });
 }
 
 extern "C" int mtp_adamw_weight_images(const mtp_wimg_desc* descs_dev, int n, int64_t total_tiles, int act_dtype, float* p_base, const float* g_base, float* m_base,
@@ -312,12 +310,7 @@ extern "C" int mtp_adamw_weight_images_lr(const mtp_wimg_desc* descs_dev, const 
 
 extern "C" int mtp_weight_images(const mtp_wimg_desc* descs_dev, int n, int64_t total_tiles, int act_dtype, mtp_stream_t stream) {
     if (!descs_dev || n <= 0 || total_tiles <= 0 || total_tiles > INT32_MAX) return MTP_ERR_ARG;
-    if (act_dtype == MTP_BF16)
-        hipLaunchKernelGGL((weight_images_kernel<bf16_t>), dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, descs_dev, n);
-    else if (act_dtype == MTP_F32)
-        hipLaunchKernelGGL((weight_images_kernel<float>), dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, descs_dev, n);
-    else return MTP_ERR_UNSUPPORTED;
-    return mtp_launch_status();
+    return for_act(act_dtype, [&](auto t) { weight_images_kernel<decltype(t)><<<(unsigned)total_tiles, kThreads, 0, (hipStream_t)stream>>>(descs_dev, n); });
 }
 
 // base[start[i] .. start[i] + count[i]) = 0 for n segments (device tables; the host splits long runs so that one workgroup clears at
@@ -332,7 +325,7 @@ __global__ __launch_bounds__(256) void zero_segments_kernel(float* __restrict__ 
 }
 extern "C" int mtp_zero_segments_f32(float* base, const int64_t* start, const int64_t* count, int n, mtp_stream_t stream) {
     if (!base || !start || !count || n <= 0) return MTP_ERR_ARG;
-    hipLaunchKernelGGL(zero_segments_kernel, dim3((unsigned)(n < 4096 ? n : 4096)), dim3(256), 0, (hipStream_t)stream, base, start, count, n);
+    zero_segments_kernel<<<dim3((unsigned)(n < 4096 ? n : 4096)), kThreads, 0, (hipStream_t)stream>>>(base, start, count, n);
     return mtp_launch_status();
 }
 
@@ -364,13 +357,13 @@ __global__ __launch_bounds__(256) void sqnorm_segments_kernel(const float* __res
 }
 extern "C" int mtp_sqnorm_segments_f32(const float* base, const int64_t* start, const int64_t* count, int n, float* out, mtp_stream_t stream) {
     if (!base || !start || !count || n <= 0 || !out) return MTP_ERR_ARG;
-    hipLaunchKernelGGL(sqnorm_segments_kernel, dim3((unsigned)(n < 4096 ? n : 4096)), dim3(256), 0, (hipStream_t)stream, base, start, count, n, out);
+    sqnorm_segments_kernel<<<dim3((unsigned)(n < 4096 ? n : 4096)), kThreads, 0, (hipStream_t)stream>>>(base, start, count, n, out);
     return mtp_launch_status();
 }
 
 extern "C" int mtp_sqnorm_f32(const float* g, float* out, int64_t n, mtp_stream_t stream) {
     if (!g || !out || n <= 0) return MTP_ERR_ARG;
-    hipLaunchKernelGGL(sqnorm_kernel, dim3(blocks_for(n / 4 + 1, 256, 2048)), dim3(256), 0, (hipStream_t)stream, g, out, n);
+    sqnorm_kernel<<<blocks_for(n / 4 + 1, kThreads, 2048), kThreads, 0, (hipStream_t)stream>>>(g, out, n);
     return mtp_launch_status();
 }
 

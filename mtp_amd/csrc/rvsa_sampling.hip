@@ -409,7 +409,7 @@ __global__ __launch_bounds__(256) void rvsa_sampling_bwd_win_kernel(const float*
 extern "C" int mtp_rvsa_sampling_bwd_win(const float* dsamp, const float* w, const float* avg, float* g, int64_t windows, int64_t C, int64_t N, mtp_stream_t stream) {
     if (!dsamp || !w || !avg || !g || windows <= 0 || C <= 0 || (C % 4) || N <= 0 || N > 4096) return MTP_ERR_ARG;
     const dim3 grid((unsigned)windows, (unsigned)((C / 4 + 63) / 64)), block(256);
-    hipLaunchKernelGGL(rvsa_sampling_bwd_win_kernel, grid, block, sizeof(float) * (size_t)N, (hipStream_t)stream, dsamp, w, avg, g, (int)C, (int)N);
+    rvsa_sampling_bwd_win_kernel<<<grid, block, sizeof(float) * (size_t)N, (hipStream_t)stream>>>(dsamp, w, avg, g, (int)C, (int)N);
     return mtp_launch_status();
 }
 
@@ -423,12 +423,10 @@ extern "C" int mtp_rvsa_sampling_fwd(const void* x, int dtype, const float* w, c
     constexpr int ysplit = 2;
     const dim3 grid((unsigned)(B * win.nh * win.nw), (unsigned)(N >= 16 * ysplit ? ysplit : 1)), block(256);
     const size_t lds = sizeof(float) * (size_t)C;
-    if (dtype == MTP_BF16)
-        hipLaunchKernelGGL((rvsa_sampling_fwd_kernel<bf16_t>), grid, block, lds, (hipStream_t)stream, (const bf16_t*)x, w, bias, avg, pooled, samp, (int)Hp, (int)Wp, (int)C, (int)N, win.pad_t, win.pad_l, win.nh, win.nw);
-    else if (dtype == MTP_F32)
-        hipLaunchKernelGGL((rvsa_sampling_fwd_kernel<float>), grid, block, lds, (hipStream_t)stream, (const float*)x, w, bias, avg, pooled, samp, (int)Hp, (int)Wp, (int)C, (int)N, win.pad_t, win.pad_l, win.nh, win.nw);
-    else return MTP_ERR_UNSUPPORTED;
-    return mtp_launch_status();
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        rvsa_sampling_fwd_kernel<T><<<grid, block, lds, (hipStream_t)stream>>>((const T*)x, w, bias, avg, pooled, samp, (int)Hp, (int)Wp, (int)C, (int)N, win.pad_t, win.pad_l, win.nh, win.nw);
+    });
 }
 /* dx (T, C) ACT += (dsamp (R, N) . w (N, C)) * leaky'(avg) / 49, broadcast over each window's tokens */
 extern "C" int mtp_rvsa_sampling_bwd(const float* dsamp, const float* w, const float* avg, void* dx, int dtype,
@@ -437,49 +435,45 @@ extern "C" int mtp_rvsa_sampling_bwd(const float* dsamp, const float* w, const f
     const RvsaWindows win(Hp, Wp);
     const dim3 grid((unsigned)(B * win.nh * win.nw), (unsigned)((C / 4 + 63) / 64)), block(256);
     const size_t lds = sizeof(float) * (size_t)N;
-    if (dtype == MTP_BF16)
-        hipLaunchKernelGGL((rvsa_sampling_bwd_kernel<bf16_t>), grid, block, lds, (hipStream_t)stream, dsamp, w, avg, (bf16_t*)dx, (int)Hp, (int)Wp, (int)C, (int)N, win.pad_t, win.pad_l, win.nh, win.nw);
-    else if (dtype == MTP_F32)
-        hipLaunchKernelGGL((rvsa_sampling_bwd_kernel<float>), grid, block, lds, (hipStream_t)stream, dsamp, w, avg, (float*)dx, (int)Hp, (int)Wp, (int)C, (int)N, win.pad_t, win.pad_l, win.nh, win.nw);
-    else return MTP_ERR_UNSUPPORTED;
-    return mtp_launch_status();
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        rvsa_sampling_bwd_kernel<T><<<grid, block, lds, (hipStream_t)stream>>>(dsamp, w, avg, (T*)dx, (int)Hp, (int)Wp, (int)C, (int)N, win.pad_t, win.pad_l, win.nh, win.nw);
+    });
 }
 
 extern "C" int mtp_rvsa_pool_fwd(const void* x, int dtype, float* avg, float* pooled, int64_t B, int64_t Hp, int64_t Wp, int64_t C, mtp_stream_t stream) {
     if (!x || !avg || !pooled || B <= 0 || (C % 4)) return MTP_ERR_ARG;
     const RvsaWindows win(Hp, Wp);
-    dim3 grid((unsigned)(B * win.nh * win.nw), (unsigned)((C / 4 + 255) / 256)), block(256);
-    if (dtype == MTP_BF16)
-        hipLaunchKernelGGL((rvsa_pool_fwd_kernel<bf16_t>), grid, block, 0, (hipStream_t)stream, (const bf16_t*)x, avg, pooled, (int)Hp, (int)Wp, (int)C, win.pad_t, win.pad_l, win.nh, win.nw);
-    else
-        hipLaunchKernelGGL((rvsa_pool_fwd_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float*)x, avg, pooled, (int)Hp, (int)Wp, (int)C, win.pad_t, win.pad_l, win.nh, win.nw);
-    return mtp_launch_status();
+    const dim3 grid((unsigned)(B * win.nh * win.nw), (unsigned)((C / 4 + 255) / 256));
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        rvsa_pool_fwd_kernel<T><<<grid, kThreads, 0, (hipStream_t)stream>>>((const T*)x, avg, pooled, (int)Hp, (int)Wp, (int)C, win.pad_t, win.pad_l, win.nh, win.nw);
+    });
 }
 extern "C" int mtp_rvsa_pool_bwd(const float* dpooled, const float* avg, void* dx, int dtype, int accumulate, int64_t B, int64_t Hp, int64_t Wp, int64_t C, mtp_stream_t stream) {
     if (!dpooled || !avg || !dx || B <= 0 || (C % 4)) return MTP_ERR_ARG;
     const RvsaWindows win(Hp, Wp);
-    dim3 grid(blocks_for(B * Hp * Wp * C / 4, 256, 8192)), block(256);
-    if (dtype == MTP_BF16)
-        hipLaunchKernelGGL((rvsa_pool_bwd_kernel<bf16_t>), grid, block, 0, (hipStream_t)stream, dpooled, avg, (bf16_t*)dx, accumulate, (int)B, (int)Hp, (int)Wp, (int)C, win.pad_t, win.pad_l, win.nh, win.nw);
-    else
-        hipLaunchKernelGGL((rvsa_pool_bwd_kernel<float>), grid, block, 0, (hipStream_t)stream, dpooled, avg, (float*)dx, accumulate, (int)B, (int)Hp, (int)Wp, (int)C, win.pad_t, win.pad_l, win.nh, win.nw);
-    return mtp_launch_status();
+    return for_act(dtype, [&](auto t) {
+        using T = decltype(t);
+        rvsa_pool_bwd_kernel<T><<<blocks_for(B * Hp * Wp * C / 4, kThreads, 8192), kThreads, 0, (hipStream_t)stream>>>(dpooled, avg, (T*)dx, accumulate, (int)B, (int)Hp, (int)Wp, (int)C,
+                                                                                                                      win.pad_t, win.pad_l, win.nh, win.nw);
+    });
 }
 
 extern "C" int mtp_small_linear_fwd(const float* x, const float* w, const float* b, float* y, int64_t R, int64_t N, int64_t K, mtp_stream_t stream) {
     if (!x || !w || !y || R <= 0 || N <= 0 || (K % 4)) return MTP_ERR_ARG;
     if (K <= 1024)
-        hipLaunchKernelGGL((small_linear_fwd_kernel<4, 4>), dim3((unsigned)((R + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, w, b, y, (int)R, (int)N, (int)K);
+        small_linear_fwd_kernel<4, 4><<<dim3((unsigned)((R + 3) / 4)), kThreads, 0, (hipStream_t)stream>>>(x, w, b, y, (int)R, (int)N, (int)K);
     else if (K <= 2048)
-        hipLaunchKernelGGL((small_linear_fwd_kernel<2, 8>), dim3((unsigned)((R + 1) / 2)), dim3(256), 0, (hipStream_t)stream, x, w, b, y, (int)R, (int)N, (int)K);
+        small_linear_fwd_kernel<2, 8><<<dim3((unsigned)((R + 1) / 2)), kThreads, 0, (hipStream_t)stream>>>(x, w, b, y, (int)R, (int)N, (int)K);
     else
-        hipLaunchKernelGGL(small_linear_fwd_generic_kernel, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, x, w, b, y, (int)N, (int)K);
+        small_linear_fwd_generic_kernel<<<(unsigned)R, kThreads, 0, (hipStream_t)stream>>>(x, w, b, y, (int)N, (int)K);
     return mtp_launch_status();
 }
 extern "C" int mtp_small_linear_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db, int64_t R, int64_t N, int64_t K, mtp_stream_t stream) {
     if (!x || !w || !dy || R <= 0 || N <= 0 || (K % 4)) return MTP_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    if (dx) hipLaunchKernelGGL(small_linear_dx_kernel, dim3((unsigned)((K + 1023) / 1024), (unsigned)((R + 3) / 4)), dim3(256), 0, s, dy, w, dx, (int)R, (int)N, (int)K);
+    if (dx) small_linear_dx_kernel<<<dim3((unsigned)((K + 1023) / 1024), (unsigned)((R + 3) / 4)), kThreads, 0, s>>>(dy, w, dx, (int)R, (int)N, (int)K);
     if (dw) {
         if (db == dw + N * K) {   // one buffer [dw | db]: one clearing pass
             (void)hipMemsetAsync(dw, 0, sizeof(float) * (size_t)(N * K + N), s);
@@ -487,8 +481,8 @@ extern "C" int mtp_small_linear_bwd(const float* x, const float* w, const float*
             (void)hipMemsetAsync(dw, 0, sizeof(float) * (size_t)(N * K), s);
             if (db) (void)hipMemsetAsync(db, 0, sizeof(float) * (size_t)N, s);
         }
-        hipLaunchKernelGGL(small_linear_dw_kernel<false>, dim3((unsigned)((K + 255) / 256), (unsigned)((N + 7) / 8), (unsigned)((R + 4 * SL_DW_ROWS - 1) / (4 * SL_DW_ROWS))), dim3(256), 0, s,
-                           dy, x, dw, db, (int)R, (int)N, (int)K, SlSegs{});
+        const dim3 grid((unsigned)((K + 255) / 256), (unsigned)((N + 7) / 8), (unsigned)((R + 4 * SL_DW_ROWS - 1) / (4 * SL_DW_ROWS)));
+        small_linear_dw_kernel<false><<<grid, kThreads, 0, s>>>(dy, x, dw, db, (int)R, (int)N, (int)K, SlSegs{});
     }
     return mtp_launch_status();
 }
@@ -509,8 +503,8 @@ extern "C" int mtp_small_linear_dw_segments(const float* x, const float* dy, int
     if (r != N) return MTP_ERR_ARG;
     seg.row0[nseg] = (int)N;
     seg.nseg = nseg;
-    hipLaunchKernelGGL(small_linear_dw_kernel<true>, dim3((unsigned)((K + 255) / 256), (unsigned)((N + 7) / 8), (unsigned)((R + 4 * SL_DW_ROWS - 1) / (4 * SL_DW_ROWS))), dim3(256), 0,
-                       (hipStream_t)stream, dy, x, (float*)nullptr, (float*)nullptr, (int)R, (int)N, (int)K, seg);
+    const dim3 grid((unsigned)((K + 255) / 256), (unsigned)((N + 7) / 8), (unsigned)((R + 4 * SL_DW_ROWS - 1) / (4 * SL_DW_ROWS)));
+    small_linear_dw_kernel<true><<<grid, kThreads, 0, (hipStream_t)stream>>>(dy, x, (float*)nullptr, (float*)nullptr, (int)R, (int)N, (int)K, seg);
     return mtp_launch_status();
 }
 
@@ -537,7 +531,6 @@ extern "C" int mtp_small_linear_dw_segments_batched(const float* const* xs, cons
         t.seg[i].nseg = nseg;
     }
     t.zsplit = (int)((R + 4 * SL_DW_ROWS - 1) / (4 * SL_DW_ROWS));
-    hipLaunchKernelGGL(small_linear_dw_batched_kernel, dim3((unsigned)((K + 255) / 256), (unsigned)((N + 7) / 8), (unsigned)(t.zsplit * count)), dim3(256), 0,
-                       (hipStream_t)stream, t, (int)R, (int)N, (int)K);
+    small_linear_dw_batched_kernel<<<dim3((unsigned)((K + 255) / 256), (unsigned)((N + 7) / 8), (unsigned)(t.zsplit * count)), kThreads, 0, (hipStream_t)stream>>>(t, (int)R, (int)N, (int)K);
     return mtp_launch_status();
 }

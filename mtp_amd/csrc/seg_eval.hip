@@ -10,20 +10,7 @@
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kMaxClasses = 256;      // 3 x 256 int32 counters per workgroup
-constexpr int kMaxBlocks = 2048;      // memory-bound: 256 CUs x 8 workgroups, the rest by grid stride
-
-template <typename T>
-__device__ __forceinline__ float4 ld4(const void* p, int64_t i) { return load4(reinterpret_cast<const T*>(p) + i); }
-__device__ __forceinline__ float4 f4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 f4scale(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
-
-inline bool dt_ok(int dt) { return dt == MTP_F32 || dt == MTP_BF16; }
-inline unsigned grid_capped(int64_t n) {
-    const int64_t g = (n + kThreads - 1) / kThreads;
-    return (unsigned)(g < kMaxBlocks ? g : kMaxBlocks);
-}
 
 // one thread per (image, crop pixel, 4 classes): resize_fwd_kernel's arithmetic (decode_head.hip) with the destination a window of a larger map
 template <typename TX>
@@ -132,10 +119,10 @@ extern "C" int mtp_seg_window_accumulate(const void* logits, int dtype, int64_t 
     MTP_CHECK_ARG(y1 >= 0 && x1 >= 0 && Hc <= H && Wc <= W && y1 <= H - Hc && x1 <= W - Wc && N * H * W < kMaxPixels);
     const int64_t total = N * Hc * Wc * (K4 / 4);
     if (dtype == MTP_F32)
-        window_accumulate_kernel<float><<<grid_capped(total), kThreads, 0, (hipStream_t)stream>>>(logits, ld, acc, lda, N, (int)h, (int)w, (int)Hc, (int)Wc, (int)H,
+        window_accumulate_kernel<float><<<blocks_for(total, kThreads, kMaxBlocks), kThreads, 0, (hipStream_t)stream>>>(logits, ld, acc, lda, N, (int)h, (int)w, (int)Hc, (int)Wc, (int)H,
                                                                                                  (int)W, (int)y1, (int)x1, K4 / 4);
     else
-        window_accumulate_kernel<bf16_t><<<grid_capped(total), kThreads, 0, (hipStream_t)stream>>>(logits, ld, acc, lda, N, (int)h, (int)w, (int)Hc, (int)Wc, (int)H,
+        window_accumulate_kernel<bf16_t><<<blocks_for(total, kThreads, kMaxBlocks), kThreads, 0, (hipStream_t)stream>>>(logits, ld, acc, lda, N, (int)h, (int)w, (int)Hc, (int)Wc, (int)H,
                                                                                                   (int)W, (int)y1, (int)x1, K4 / 4);
     return mtp_launch_status();
 }
@@ -147,7 +134,7 @@ extern "C" int mtp_seg_argmax_areas(float* acc, int64_t lda, int64_t N, int64_t 
     MTP_CHECK_ARG(lda >= (K + 3) / 4 * 4 && (lda % 4) == 0 && ((uintptr_t)acc & 15) == 0);
     MTP_CHECK_ARG((cy == nullptr) == (cx == nullptr) && (labels == nullptr) == (areas == nullptr) && (!labels || label_bytes == 1 || label_bytes == 8));
     MTP_CHECK_ARG(pred || seg_logits || areas || write_back);
-    const unsigned g = grid_capped(N * H * W);
+    const unsigned g = blocks_for(N * H * W, kThreads, kMaxBlocks);
     unsigned long long* ar = reinterpret_cast<unsigned long long*>(areas);
     hipStream_t s = (hipStream_t)stream;
     if (labels && label_bytes == 8)
@@ -163,7 +150,7 @@ extern "C" int mtp_seg_areas(const void* pred, int pred_bytes, const void* label
                              mtp_stream_t stream) {
     MTP_CHECK_ARG(pred && labels && areas && pixels > 0 && pixels < kMaxPixels && K > 0 && K <= kMaxClasses);
     MTP_CHECK_ARG((pred_bytes == 1 || pred_bytes == 8) && (label_bytes == 1 || label_bytes == 8));
-    const unsigned g = grid_capped(pixels);
+    const unsigned g = blocks_for(pixels, kThreads, kMaxBlocks);
     unsigned long long* ar = reinterpret_cast<unsigned long long*>(areas);
     hipStream_t s = (hipStream_t)stream;
     if (pred_bytes == 1 && label_bytes == 1)

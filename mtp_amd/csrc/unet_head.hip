@@ -10,19 +10,9 @@
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kTile = 64;       // fuse_pair: positions x channels per workgroup
 
-template <typename T>
-__device__ __forceinline__ float4 ld4(const void* p, int64_t i) { return load4(reinterpret_cast<const T*>(p) + i); }
-template <typename T>
-__device__ __forceinline__ void st4(void* p, int64_t i, float4 v) { store4(reinterpret_cast<T*>(p) + i, v); }
-__device__ __forceinline__ float4 f4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 f4scale(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
-
-inline bool dt_ok(int dt) { return dt == MTP_F32 || dt == MTP_BF16; }
 inline bool policy_ok(int p) { return p == MTP_FUSE_CONCAT || p == MTP_FUSE_SUM || p == MTP_FUSE_DIFF || p == MTP_FUSE_ABS_DIFF; }
-inline unsigned grid1(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
 // ---------------------------------------------------------------------------------------------------------------- fuse_pair
 __device__ __forceinline__ float fuse1(float a, float b, int policy) {
@@ -188,16 +178,9 @@ extern "C" int mtp_fuse_pair_fwd(const void* f, int f_dtype, void* out, int out_
     const dim3 grid((unsigned)((S + kTile - 1) / kTile), (unsigned)((C + kTile - 1) / kTile), (unsigned)nz);
     const bool vec = (S % 4) == 0 && ((uintptr_t)f & 15) == 0;
     hipStream_t s = (hipStream_t)stream;
-#define MTP_FUSE_FWD(TI, TO)                                                                                                              \
-    do {                                                                                                                                  \
-        if (vec) fuse_pair_fwd_kernel<TI, TO, true><<<grid, kThreads, 0, s>>>((const TI*)f, (TO*)out, ld, N, C, S, policy);               \
-        else fuse_pair_fwd_kernel<TI, TO, false><<<grid, kThreads, 0, s>>>((const TI*)f, (TO*)out, ld, N, C, S, policy);                  \
-    } while (0)
-    if (f_dtype == MTP_F32 && out_dtype == MTP_F32) MTP_FUSE_FWD(float, float);
-    else if (f_dtype == MTP_F32) MTP_FUSE_FWD(float, bf16_t);
-    else if (out_dtype == MTP_F32) MTP_FUSE_FWD(bf16_t, float);
-    else MTP_FUSE_FWD(bf16_t, bf16_t);
-#undef MTP_FUSE_FWD
+    MTP_DISPATCH2(f_dtype, out_dtype,
+                  if (vec) fuse_pair_fwd_kernel<TA, TB, true><<<grid, kThreads, 0, s>>>((const TA*)f, (TB*)out, ld, N, C, S, policy);
+                  else fuse_pair_fwd_kernel<TA, TB, false><<<grid, kThreads, 0, s>>>((const TA*)f, (TB*)out, ld, N, C, S, policy));
     return mtp_launch_status();
 }
 
@@ -224,13 +207,8 @@ extern "C" int mtp_unet_up_cat_fwd(const void* x, int64_t ldx, int64_t Cx, const
     const int64_t threads = N * 4 * h * w * ((Cx + Cs) / 4);
     MTP_CHECK_ARG(fits_grid(threads));
     hipStream_t s = (hipStream_t)stream;
-#define MTP_UP_CAT(TX, TY) \
-    up_cat_fwd_kernel<TX, TY><<<grid1(threads), kThreads, 0, s>>>(x, ldx, Cx, skip, lds, Cs, y, ldy, N, (int)h, (int)w, (int)hs, (int)ws)
-    if (in_dtype == MTP_F32 && y_dtype == MTP_F32) MTP_UP_CAT(float, float);
-    else if (in_dtype == MTP_F32) MTP_UP_CAT(float, bf16_t);
-    else if (y_dtype == MTP_F32) MTP_UP_CAT(bf16_t, float);
-    else MTP_UP_CAT(bf16_t, bf16_t);
-#undef MTP_UP_CAT
+    MTP_DISPATCH2(in_dtype, y_dtype,
+                  up_cat_fwd_kernel<TA, TB><<<blocks_exact(threads), kThreads, 0, s>>>(x, ldx, Cx, skip, lds, Cs, y, ldy, N, (int)h, (int)w, (int)hs, (int)ws));
     return mtp_launch_status();
 }
 
@@ -241,7 +219,7 @@ extern "C" int mtp_unet_up_cat_bwd(const float* dy, int64_t lddy, float* dx, int
     MTP_CHECK_ARG(Cs >= 0 && (Cs % 4) == 0 && lddx >= Cx && (lddx % 4) == 0 && lddy >= Cx + Cs && (lddy % 4) == 0);
     const int64_t threads = N * h * w * (Cx / 4);
     MTP_CHECK_ARG(fits_grid(threads));
-    up_bwd_kernel<<<grid1(threads), kThreads, 0, (hipStream_t)stream>>>(dy, lddy, dx, lddx, Cx, N, (int)h, (int)w, accumulate);
+    up_bwd_kernel<<<blocks_exact(threads), kThreads, 0, (hipStream_t)stream>>>(dy, lddy, dx, lddx, Cx, N, (int)h, (int)w, accumulate);
     const int rc = mtp_launch_status();
     if (rc != 0 || Cs == 0) return rc;
     // the skip's bilinear adjoint: the resize backward's gather on the column slice [Cx, Cx + Cs)

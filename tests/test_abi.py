@@ -130,3 +130,132 @@ def test_every_entry_point_rejects_null_arguments_before_launching():
             continue
         args = [0.0 if a is C.c_float else (None if (a is C.c_void_p or hasattr(a, "contents")) else 0) for a in argtypes]
         assert getattr(lib, name)(*args) == -1, name
+
+
+# ---- every entry point that takes a dtype refuses an unknown one before it launches --------------------------------------------------------------
+# One passing argument tuple per entry point: plausible sizes, P = a non-NULL (16-byte aligned, never dereferenced) pointer, D = the dtype under test.
+# With a valid dtype every tuple passes its entry point's argument checks and reaches the launch; the test puts an unknown value into every D.
+_P, _D = 1 << 20, "dtype"
+_DTYPE_REFUSALS = {
+    "mtp_layernorm_fwd": (_P, _D, _P, _P, _P, _D, _P, _P, 4, 8, 1e-6, 0, None),
+    "mtp_layernorm_bwd": (_P, _D, _P, _D, _P, _P, _P, _P, 0, None, None, _P, _D, None, _D, None, 0, _P, _P, 0, 4, 8, None),
+    "mtp_layernorm_bwd_win": (_P, _D, _P, _D, _P, _P, _P, None, None, _P, _D, None, _D, None, 0, _P, _P, 0, 49, 8, _P, 1, 7, 7, None),
+    "mtp_layernorm_residual_fwd": (_P, _D, _P, _P, _P, _P, None, 0, _P, _P, _P, _P, 4, 8, 1e-6, None),
+    "mtp_layernorm_residual_bwd": (_P, _P, _D, _P, _P, _P, _P, _P, None, 0, _P, _P, 4, 8, None),
+    "mtp_colsum": (_P, _D, 8, _P, 4, 8, None),
+    "mtp_colsum_acc": (_P, _D, 8, _P, 4, 8, None),
+    "mtp_patchify": (_P, _P, _D, 1, 3, 16, 16, 4, None),
+    "mtp_unpatchify": (_P, _D, _P, 1, 3, 16, 16, 4, None),
+    "mtp_preprocess_patchify": (_P, _P, _D, 1, 16, 16, 4, 4, "mean", "std", 0, 0.0, None),      # mean / std are read on the host: real arrays
+    "mtp_cast": (_P, _D, _P, _D, 8, None),
+    "mtp_transpose_cast": (_P, _P, _D, 4, 8, None),
+    "mtp_weight_images": (_P, 1, 1, _D, None),
+    "mtp_adamw_weight_images": (_P, 1, 1, _D, _P, _P, _P, _P, _P, None, 0.0, 1.0, None),
+    "mtp_adamw_weight_images_lr": (_P, _P, 1, 1, _D, _P, _P, _P, _P, _P, None, 0.0, 1.0, None),
+    "mtp_convt_pack": (_P, _P, _P, _D, 8, 8, None),
+    "mtp_tokens_to_nchw": (_P, _D, _P, _D, 1, 2, 2, 8, 0, None),
+    "mtp_nchw_to_tokens": (_P, _D, _P, _D, 1, 2, 2, 8, 0, None),
+    "mtp_maxpool2_tokens_fwd": (_P, _P, _D, 1, 2, 2, 8, None),
+    "mtp_maxpool2_tokens_bwd": (_P, _P, _D, _P, 0, 1, 2, 2, 8, None),
+    "mtp_scale_rows_cast": (_P, _P, _D, None, 0, 4, 8, None),
+    "mtp_im2col3x3": (_P, _D, 128, 32, 8, 1, _P, _D, 1, 4, 4, 8, 1, 72, None),
+    "mtp_col2im3x3": (_P, _D, _P, 128, 32, 8, 1, 1, 4, 4, 8, 1, 72, 0, None),
+    "mtp_conv3x3_pack": (_P, _P, _P, _D, 8, 8, 72, None),
+    "mtp_pack_rows_padded": (_P, _P, _P, _D, 4, 8, 8, None),
+    "mtp_cast_pad_rows": (_P, 4, _P, _D, 8, 4, None),
+    "mtp_copy_rows": (_P, 8, _P, 8, _D, 4, 4, None),
+    "mtp_dwconv3x3_fwd": (_P, _P, _P, _P, _D, 1, 4, 4, 8, None),
+    "mtp_dwconv3x3_bwd_dx": (_P, _D, _P, _P, 0, 1, 4, 4, 8, None),
+    "mtp_dwconv3x3_bwd_dw": (_P, _P, _D, _P, 1, 4, 4, 8, None),
+    "mtp_dwconv_fwd": (_P, _P, _P, _P, _D, 1, 4, 4, 8, 5, None),
+    "mtp_dwconv_bwd_dx": (_P, _D, _P, _P, 0, 1, 4, 4, 8, 5, None),
+    "mtp_dwconv_bwd_dw": (_P, _P, _D, _P, _P, 1, 4, 4, 8, 5, None),
+    "mtp_center_feature_scale_fwd": (_P, _P, _P, 2, _P, _D, 4, 2, 4, None),
+    "mtp_center_feature_scale_bwd": (_P, _P, _P, _P, 2, _P, _P, _P, _D, 4, 2, 4, None),
+    "mtp_softmax_groups_fwd": (_P, 18, _P, _D, 4, 2, 9, None),
+    "mtp_softmax_groups_bwd": (_P, _P, _P, 18, _D, 4, 2, 9, None),
+    "mtp_scale_residual_fwd": (_P, _P, _D, _P, None, 0, _P, _P, 4, 8, None),
+    "mtp_scale_residual_bwd": (_P, _P, _D, _P, None, 0, _P, _P, 4, 8, None),
+    "mtp_full_attn_fwd": (_P, _P, _P, _D, _P, _P, 1, 14, 14, 2, 64, 0.125, None),
+    "mtp_full_attn_bwd": (_P, _P, _P, _P, _P, _D, _P, _P, _P, _P, 1, 14, 14, 2, 64, 0.125, None),
+    "mtp_full_attn_kernel": (_D, 14, 14, 0),
+    "mtp_rvsa_attn_kernel": (_D, 14, 14, 2, 0),
+    "mtp_rvsa_pool_fwd": (_P, _D, _P, _P, 1, 7, 7, 8, None),
+    "mtp_rvsa_pool_bwd": (_P, _P, _P, _D, 0, 1, 7, 7, 8, None),
+    "mtp_rvsa_sampling_fwd": (_P, _D, _P, _P, _P, _P, _P, 1, 7, 7, 8, 4, None),
+    "mtp_rvsa_sampling_bwd": (_P, _P, _P, _P, _D, 1, 7, 7, 8, 4, None),
+    "mtp_rvsa_attn_fwd": (_P, _P, _P, _P, _D, _P, _P, _P, 1, 7, 7, 2, 64, 0.125, None),
+    "mtp_rvsa_attn_bwd": (_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _D, _P, _P, _P, 1, 7, 7, 2, 64, 0.125, None),
+    "mtp_dcnv3_fwd": (_P, _P, _P, _P, _D, "geom", None),
+    "mtp_dcnv3_bwd": (_P, _P, _P, _P, _D, _P, _P, _P, "geom", None),
+    "mtp_dcnv3_bwd_act": (_P, _P, _P, _P, _D, _P, _P, _P, _P, 18, "geom", None),
+    "mtp_dcnv3_kernel": (_P, _P, _P, _P, None, None, None, _D, "geom", 0),
+    "mtp_comm_allreduce_bucket_dt": (_P, _P, 8, _D, None),
+    "mtp_comm_reduce_scatter_bucket": (_P, _P, 8, 0, _D, None),
+    "mtp_comm_allgather_bucket": (_P, _P, 8, 0, _D, None),
+    "mtp_bn_stats": (_P, _D, 8, None, _P, _P, 4, 8, None),
+    "mtp_bn_apply": (_P, _D, 8, _P, _P, _P, _P, 0, _P, _D, 8, 4, 8, None),
+    "mtp_bn_bwd_stats": (_P, _D, 8, _P, _D, 8, _P, _P, _P, _P, 0, _P, _P, 4, 8, None),
+    "mtp_bn_bwd_dx": (_P, _D, 8, _P, _D, 8, _P, _P, _P, _P, 0, None, 0.0, _P, _D, 8, 4, 8, None),
+    "mtp_resize_bilinear_fwd": (_P, _D, 8, _P, _D, 8, 1, 2, 2, 4, 4, 8, 0, None),
+    "mtp_resize_bilinear_bwd": (_P, _D, 8, _P, 8, 1, 2, 2, 4, 4, 8, 0, None),
+    "mtp_adaptive_avg_pool_fwd": (_P, _D, 8, _P, _D, 1, 4, 4, 8, 2, None),
+    "mtp_adaptive_avg_pool_bwd": (_P, _D, _P, 8, 1, 4, 4, 8, 2, 0, None),
+    "mtp_channel_scale": (_P, _D, 8, _P, 4, _P, _D, 8, 4, 8, None),
+    "mtp_seg_ce": (_P, _D, 4, 1, 2, 2, 3, _P, 1, 4, 4, 255, 1.0, _P, _P, 4, _P, 1 << 16, None),
+    "mtp_seg_window_accumulate": (_P, _D, 4, 1, 2, 2, 3, _P, 4, 4, 4, 0, 0, 4, 4, None),
+    "mtp_fuse_pair_fwd": (_P, _D, _P, _D, 8, 1, 8, 2, 2, 1, None),
+    "mtp_fuse_pair_bwd": (_P, 8, _P, _D, _P, 1, 8, 2, 2, 3, None),      # policy abs_diff: the only one that reads f
+    "mtp_unet_up_cat_fwd": (_P, 8, 8, None, 0, 0, _D, _P, _D, 8, 1, 2, 2, 0, 0, None),
+    "mtp_gap_fwd": (_P, _D, _P, 1, 8, 4, None),
+    "mtp_gap_bwd": (_P, _P, _D, 1, 8, 4, None),
+}
+# not in the table: the dtype arrives inside a struct, and no other argument of a passing call can carry an unknown one
+_DTYPE_IN_STRUCT = {
+    "mtp_gemm_nt": "mtp_gemm_args.in_dtype / out_dtype", "mtp_gemm_tn": "mtp_gemm_args", "mtp_gemm_tn_grouped": "mtp_gemm_args",
+    "mtp_gemm_nt_plan": "mtp_gemm_args", "mtp_gemm_nt_workspace_bytes": "mtp_gemm_args",
+}
+# a query with its own contract (the test above pins it): an unsupported dtype is the family NONE, and a query launches nothing
+_DTYPE_QUERY_NONE = "mtp_conv_kernel"
+
+
+def _takes_dtype():
+    """the entry points of include/mtp_hip.h with a dtype among their parameters"""
+    src = open(os.path.join(ROOT, "include", "mtp_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    out = []
+    for name, params in re.findall(r"\b(mtp_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src):
+        if re.search(r"\bint (\w+_)?dtype\b", params):
+            out.append(name)
+    return sorted(out)
+
+
+def test_every_entry_point_refuses_an_unknown_dtype_before_launching():
+    """dtype = 7 (nothing) and MTP_F64 (a real value that only DCNv3 takes) with every other argument valid: a negative return, i.e. the argument
+    checks or the dispatcher refused.  Without a device an attempted launch comes back as a positive hipError_t, which is what this test catches;
+    the pointers are fake, so with a device in sight it must not run."""
+    import ctypes as C
+    import pytest
+    import torch
+    from mtp_amd import _lib
+    if torch.cuda.is_available():
+        pytest.skip("fake device pointers: only where a launch cannot reach a device")
+    lib = _lib.load()
+    names = _takes_dtype()
+    assert len(names) >= 70
+    assert sorted(set(names) - {_DTYPE_QUERY_NONE}) == sorted(_DTYPE_REFUSALS), "an entry point with a dtype and no argument tuple (or the reverse)"
+    assert all(n in _lib.SIGNATURES and not re.search(r"dtype", n) for n in _DTYPE_IN_STRUCT)
+    geom = _lib.Dcnv3Geom(N=1, H=4, W=4, kernel_h=3, kernel_w=3, stride_h=1, stride_w=1, pad_h=1, pad_w=1, dilation_h=1, dilation_w=1, group=1,
+                          group_channels=16, offset_scale=1.0, im2col_step=1)
+    norm = (C.c_float * 3)(1.0, 1.0, 1.0)
+    held = {"geom": C.byref(geom), "mean": norm, "std": norm}
+    f64_ok = {"mtp_dcnv3_fwd", "mtp_dcnv3_bwd", "mtp_dcnv3_kernel"}
+    for bad in (7, 2):
+        for name, tup in sorted(_DTYPE_REFUSALS.items()):
+            if bad == 2 and name in f64_ok:
+                continue
+            assert len(tup) == len(_lib.SIGNATURES[name][1]), name
+            args = [bad if a is _D else held.get(a, a) if isinstance(a, str) else a for a in tup]
+            assert getattr(lib, name)(*args) < 0, (name, bad)
+        for op in range(5):
+            assert lib.mtp_conv_kernel(op, _P, bad, 128, 32, 8, 1, _P, bad, _P, None, 1, 4, 4, 8, 1, 72) == _lib.CONV_KERNEL_NONE, (op, bad)
