@@ -139,6 +139,37 @@ int mtp_gemm_nt_plan(const mtp_gemm_args* args, int cus, struct mtp_gemm_nt_plan
 int mtp_gemm_nt_tile(const mtp_gemm_args* args);
 /* bytes of `workspace` mtp_gemm_nt wants: 0 since round 4 (kept in the ABI for callers compiled against 0.3) */
 int64_t mtp_gemm_nt_workspace_bytes(void);
+/* mtp_gemm_nt with a rider: a small operator that is independent of the GEMM and runs on the compute units its launch leaves idle.  The P8 family runs one
+ * workgroup per CU, and M = 12544 gives every ViT-L shape 224, 672 or 896 tiles: 224 workgroups finish in the same 1, 3 or 4 rounds as 256 do, so 32 CUs are
+ * free for the whole launch.  Up to 32 extra workgroups of the SAME launch do the rider's work there -- no second stream, no event, no extra launch, and no
+ * workgroup waits on another.  Where the problem cannot carry the rider (another kernel family, no spare CU, an instantiation that does not exist) the GEMM
+ * and the rider's stand-alone kernel are launched one after the other on `stream`.  Either way C equals mtp_gemm_nt's and the rider's outputs equal its
+ * stand-alone entry point's, bit for bit.
+ *   MTP_NT_RIDER_SAMPLING_FWD      mtp_rvsa_sampling_fwd (x, w, bias -> avg, pooled, samp; B, Hp, Wp, C, N); rides a persistent bf16 launch
+ *   MTP_NT_RIDER_SAMPLING_BWD_WIN  mtp_rvsa_sampling_bwd_win (dsamp, w, avg -> g; windows, C, N); rides a one-round bf16 launch
+ *   MTP_NT_RIDER_NONE              no operator: where riders could be carried, the GEMM alone on the workgroups it would then have (A/B of that walk)
+ * MTP_ERR_ARG for NULL arguments, an unknown kind or sizes the stand-alone entry point refuses; MTP_ERR_UNSUPPORTED for an activation dtype other than
+ * bf16 (use the two entry points); both before anything is launched. */
+enum { MTP_NT_RIDER_NONE = 0, MTP_NT_RIDER_SAMPLING_FWD = 1, MTP_NT_RIDER_SAMPLING_BWD_WIN = 2 };
+struct mtp_nt_rider {
+    int kind;             /* MTP_NT_RIDER_* */
+    int act_dtype;        /* mtp_dtype of x (forward) */
+    const void* x;        /* forward: (B * Hp * Wp, C) activations */
+    const float* dsamp;   /* backward: (windows, N) */
+    const float* w;       /* (N, C) stacked heads */
+    const float* bias;    /* forward: (N) or NULL */
+    float* avg;           /* (windows, C): forward out, backward in */
+    float* pooled;        /* forward out (windows, C) */
+    float* samp;          /* forward out (windows, N) */
+    float* g;             /* backward out (windows, C) */
+    int64_t B, Hp, Wp;    /* forward: the token grid */
+    int64_t windows;      /* backward */
+    int64_t C, N;
+};
+int mtp_gemm_nt_rider(const mtp_gemm_args* args, const struct mtp_nt_rider* rider, mtp_stream_t stream);
+/* GEMM workgroups of a P8 launch of `ntiles` tiles that carries riders on `cus` compute units: the fewest that still finish in ceil(ntiles / cus) rounds
+ * (the other cus - result CUs are spare).  Host arithmetic, no device needed; MTP_ERR_ARG unless both are positive. */
+int mtp_nt_p8_gemm_wgs(int ntiles, int cus);
 /* weight gradient: C[m][n] = sum_k A[k][m] * B[k][n]  (dW = dY^T X), f32 output. */
 int mtp_gemm_tn(const mtp_gemm_args* args, mtp_stream_t stream);
 /* Grouped weight gradients: `count` (<= MTP_MAX_GROUPED_GEMMS) independent problems C_i (M_i, N_i) f32 = A_i (K_i, M_i)^T B_i (K_i, N_i)

@@ -57,6 +57,16 @@ class GemmNtPlan(C.Structure):
     _fields_ = [("family", i32), ("tile_m", i32), ("order", i32), ("persistent", i32), ("store_policy", i32)]
 
 
+# kinds of struct mtp_nt_rider (mtp_gemm_nt_rider)
+NT_RIDER_NONE, NT_RIDER_SAMPLING_FWD, NT_RIDER_SAMPLING_BWD_WIN = 0, 1, 2
+
+
+class NtRider(C.Structure):
+    """struct mtp_nt_rider"""
+    _fields_ = [("kind", i32), ("act_dtype", i32), ("x", p), ("dsamp", p), ("w", p), ("bias", p), ("avg", p), ("pooled", p), ("samp", p), ("g", p),
+                ("B", i64), ("Hp", i64), ("Wp", i64), ("windows", i64), ("C", i64), ("N", i64)]
+
+
 class WimgDesc(C.Structure):
     """mtp_wimg_desc"""
     _fields_ = [("src", p), ("w", p), ("wt", p), ("R", i64), ("C", i64), ("tile0", i64), ("f32_out", C.c_int32), ("wd", C.c_float)]
@@ -87,6 +97,8 @@ SIGNATURES = {
     "mtp_gemm_nt_plan": (i32, [C.POINTER(GemmArgs), i32, C.POINTER(GemmNtPlan)]),
     "mtp_gemm_nt_tile": (i32, [C.POINTER(GemmArgs)]),
     "mtp_gemm_nt_workspace_bytes": (i64, []),
+    "mtp_gemm_nt_rider": (i32, [C.POINTER(GemmArgs), C.POINTER(NtRider), p]),
+    "mtp_nt_p8_gemm_wgs": (i32, [i32, i32]),
     "mtp_gemm_tn": (i32, [C.POINTER(GemmArgs), p]),
     "mtp_gemm_tn_grouped": (i32, [C.POINTER(GemmArgs), i32, p]),
     "mtp_sum_partials_batch": (i32, [p, p, p, p, i32, p]),

@@ -740,6 +740,43 @@ extern "C" int mtp_gemm_nt(const mtp_gemm_args* a, mtp_stream_t stream) {
     return MTP_ERR_UNSUPPORTED;
 }
 
+// The GEMM with a rider (include/mtp_hip.h).  Every argument check precedes the first launch; a problem that cannot carry the rider falls back to the two
+// launches it replaces, in the order GEMM, stand-alone kernel.
+extern "C" int mtp_gemm_nt_rider(const mtp_gemm_args* a, const struct mtp_nt_rider* r, mtp_stream_t stream) {
+    if (!a || !r) return MTP_ERR_ARG;
+    P8Rider k8{};
+    if (r->kind == MTP_NT_RIDER_SAMPLING_FWD) {      // the checks of mtp_rvsa_sampling_fwd
+        if (!r->x || !r->w || !r->avg || !r->pooled || !r->samp || r->B <= 0 || r->Hp <= 0 || r->Wp <= 0 || r->C <= 0 || (r->C % 4) || r->C > 8192 || r->N <= 0) return MTP_ERR_ARG;
+        if (r->act_dtype != MTP_BF16) return MTP_ERR_UNSUPPORTED;
+        const RvsaWindows win(r->Hp, r->Wp);
+        if (r->B * win.nh * win.nw > INT32_MAX || r->N > INT32_MAX) return MTP_ERR_ARG;
+        k8.windows = (int)(r->B * win.nh * win.nw);
+        k8.Hp = (int)r->Hp; k8.Wp = (int)r->Wp; k8.pad_t = win.pad_t; k8.pad_l = win.pad_l; k8.nh = win.nh; k8.nw = win.nw;
+    } else if (r->kind == MTP_NT_RIDER_SAMPLING_BWD_WIN) {      // the checks of mtp_rvsa_sampling_bwd_win
+        if (!r->dsamp || !r->w || !r->avg || !r->g || r->windows <= 0 || r->windows > INT32_MAX || r->C <= 0 || (r->C % 4) || r->C > INT32_MAX || r->N <= 0 || r->N > 4096) return MTP_ERR_ARG;
+        k8.windows = (int)r->windows;
+    } else if (r->kind != MTP_NT_RIDER_NONE) {
+        return MTP_ERR_ARG;
+    }
+    k8.C = (int)r->C; k8.N = (int)r->N;
+    k8.x = r->x; k8.dsamp = r->dsamp; k8.w = r->w; k8.bias = r->bias; k8.avg = r->avg; k8.pooled = r->pooled; k8.samp = r->samp; k8.g = r->g;
+    hipStream_t s = (hipStream_t)stream;
+    if (a->in_dtype == MTP_BF16 && a->out_dtype == MTP_BF16 && a->epilogue == MTP_EPI_BIAS) {
+        KArgs k;
+        if (const int rc = fill_common<bf16_t>(a, k)) return rc;
+        if ((a->K % Elem<bf16_t>::kPerChunk) || (a->bias && a->bias_mod > 0 && (a->bias_mod % 4))) return MTP_ERR_ARG;
+        const NtPlan plan = nt_plan(a, k, mtp_stream_cus(s));
+        if (plan.family == MTP_GEMM_NT_FAMILY_P8) {
+            const int rc = mtp_nt_p8_launch_rider(k, a->out_dtype, a->epilogue, plan, r->kind, k8, s);
+            if (rc != MTP_ERR_UNSUPPORTED) return rc;
+        }
+    }
+    if (const int rc = mtp_gemm_nt(a, stream)) return rc;
+    if (r->kind == MTP_NT_RIDER_SAMPLING_FWD) return mtp_rvsa_sampling_fwd(r->x, r->act_dtype, r->w, r->bias, r->avg, r->pooled, r->samp, r->B, r->Hp, r->Wp, r->C, r->N, stream);
+    if (r->kind == MTP_NT_RIDER_SAMPLING_BWD_WIN) return mtp_rvsa_sampling_bwd_win(r->dsamp, r->w, r->avg, r->g, r->windows, r->C, r->N, stream);
+    return 0;
+}
+
 // (round 4: the stream-K form that used `workspace` was removed -- measured slower; the query stays in the ABI and answers 0)
 extern "C" int64_t mtp_gemm_nt_workspace_bytes(void) { return 0; }
 

@@ -27,6 +27,21 @@ struct KArgs {
     float* colsum;          // TN (transpose-read kernel): colsum[m] += sum_k A[k][m], or nullptr
 };
 
+// what the rider workgroups of one GEMM launch need: the operator's pointers and sizes, and how the launch is split
+struct P8Rider {
+    int gemm_wgs, riders;      // workgroups [0, gemm_wgs) run the GEMM, [gemm_wgs, gemm_wgs + riders) ride
+    int windows;               // work items: window `r + i * riders` for rider r, i = 2 * iteration + half
+    int Hp, Wp, C, N, pad_t, pad_l, nh, nw;
+    const void* x;             // forward: the (T, C) activation the GEMM reads too
+    const float* dsamp;        // backward
+    const float* w;
+    const float* bias;
+    float* avg;                // forward: out; backward: in
+    float* pooled;
+    float* samp;
+    float* g;
+};
+
 typedef struct mtp_gemm_nt_plan NtPlan;   // what mtp_gemm_nt runs a problem on (include/mtp_hip.h); filled by nt_plan() in gemm.hip, the only reader of the NT flags of args.variant
 
 // gemm_p8.hip: 224 / 256 x 256 x 64 tile, 8 waves, 8-phase LDS-DMA pipeline (bf16 NT, complete K tiles).  Runs what the plan says: tile_m, order, persistent,
@@ -35,6 +50,9 @@ int mtp_nt_p8_launch(const KArgs& k, int out_dtype, int epilogue, const NtPlan& 
 int mtp_nt_p8_fits(const KArgs& k, int out_dtype, int epilogue);   // 1 when mtp_nt_p8_launch would run the problem
 int mtp_nt_p8_tiles(int64_t M, int64_t N, int tile_m);             // tiles of tile_m rows the kernel cuts an (M, N) output into
 int mtp_nt_p8_pick_tile_m(int64_t M, int64_t N, int64_t cus);      // the cheaper of 256- and 224-row tiles on `cus` CUs
+// the same launch with up to 32 rider workgroups on the CUs the GEMM leaves idle (kind: MTP_NT_RIDER_*; rider.gemm_wgs / riders are filled here).
+// MTP_ERR_UNSUPPORTED, nothing launched, when the problem cannot carry the rider: the caller launches the two kernels one after the other.
+int mtp_nt_p8_launch_rider(const KArgs& k, int out_dtype, int epilogue, const NtPlan& plan, int kind, const P8Rider& rider, hipStream_t stream);
 // gemm_s8.hip: 128 x 256 x 64 strips, 8 waves, two accumulator sets: the epilogue of a strip runs under the next strip's K loop
 // (bf16 NT, K >= 704 in whole K-tiles).  order: 1 = plain strip order.  MTP_ERR_UNSUPPORTED when the problem does not fit.
 int mtp_nt_s8_launch(const KArgs& k, int out_dtype, int epilogue, int order, hipStream_t stream);

@@ -36,6 +36,7 @@
 // * Accumulation order per output element is the same as in gemm.hip (k ascending, one MFMA per 32 k): results are
 //   bit-identical to the 128-wide kernels.
 #include "gemm_p8.h"
+#include "rvsa_sampling_body.h"
 
 namespace {
 
@@ -157,9 +158,65 @@ __device__ __forceinline__ void p8_issue_prologue(P8Ctx& c) {
 // through 4 KiB per wave beyond the ring: the first-load latency of a tile and the workgroup hand-over are hidden behind the
 // previous tile's stores.  The load queue is drained (vmcnt(0)) once per tile, after the epilogue: the counted waits of the main
 // loop assume that only the DMA stream is in flight.
-template <typename Tout, int EPI, int MI1, int XP, int PS, int SP = 0>
-__global__ __launch_bounds__(P8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_nt_p8_kernel(KArgs p) {
+// One rider workgroup (512 threads, KIND 1 = sampling forward, 2 = backward window factor) takes the windows rider, rider + riders, ...  Every trip count
+// comes from the launch arguments alone, so every barrier below is reached by all 512 threads.  smem: the launch's dynamic LDS.
+// pooled rows one pass of the heads serves: a rider of the ViT-L step at batch 64 (256 windows on 32 riders) has 8 and makes two rounds of passes; with 8 rows
+// per pass the kernel spills 62 VGPRs, with 4 it uses 249 and no scratch
+constexpr int P8_RIDER_ROWS = 4;
+template <int KIND>
+__device__ __forceinline__ void p8_rider_run(const P8Rider& r, int rider, char* smem) {
+    const int half = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8), tid = (int)threadIdx.x & 255;
+    const int per = (r.windows + r.riders - 1) / r.riders;      // windows per rider
+    if constexpr (KIND == 1) {
+        // forward: the two halves pool the rider's windows into one LDS row each (C floats per window), then all 8 waves make the head outputs of up to
+        // P8_RIDER_ROWS windows per pass -- a weight vector is loaded once for all of them (measured: window by window, each rider CU reading the 320 KB
+        // of weights once per window, the riders outlasted the qkv GEMM, 90 against 70 us; this way the launch is 3 us longer than the GEMM alone)
+        float* pl = reinterpret_cast<float*>(smem);
+        for (int s0 = 0; s0 < per; s0 += 2) {
+            const int item = rider + (s0 + half) * r.riders;
+            const bool live = s0 + half < per && item < r.windows;
+            rvsa_pool_window<bf16_t, 4>((const bf16_t*)r.x, r.avg, r.pooled, r.Hp, r.Wp, r.C, r.pad_t, r.pad_l, r.nh, r.nw, live ? item : r.windows - 1, live, tid,
+                                        pl + (int64_t)(s0 + half) * r.C);
+        }
+        __syncthreads();
+        for (int g0 = 0; g0 < per; g0 += P8_RIDER_ROWS)      // (rows past `per` hold clamped windows or belong to nobody: read, never stored)
+            rvsa_heads<P8_RIDER_ROWS>(r.w, r.bias, r.samp, r.C, r.N, 0, r.N, (int)threadIdx.x >> 6, 8, (int)threadIdx.x & 63, pl + (int64_t)g0 * r.C,
+                                      rider + g0 * r.riders, r.riders, r.windows);
+    } else {
+        // backward: the halves take windows rider + (2 it + half) * riders, 64 channel quads per call
+        // (no barrier between the calls: a call's first barrier separates the previous call's reads of `part` from its own writes, its
+        //  second the reads of `ds` from the next call's writes)
+        char* mine = smem + half * (4096 + ((r.N * 4 + 15) & ~15));
+        for (int it = 0; it < (per + 1) / 2; ++it) {
+            const int item = rider + (2 * it + half) * r.riders;
+            const bool live = item < r.windows;
+            for (int c4base = 0; c4base < r.C / 4; c4base += 64)
+                rvsa_sampling_bwd_win_body(r.dsamp, r.w, r.avg, r.g, r.C, r.N, live ? item : r.windows - 1, c4base, live, tid, reinterpret_cast<float*>(mine + 4096),
+                                           reinterpret_cast<float4*>(mine));
+        }
+    }
+}
+
+// RK = rider kind (0 none, 1 RVSA sampling forward, 2 sampling backward window factor): the launch has p.rider.gemm_wgs + p.rider.riders workgroups.
+// The GEMM workgroups are picked so that every one of them walks the same number of tiles (mtp_nt_p8_gemm_wgs: 224 of 256 on every ViT-L shape), which
+// lasts as long as the uneven walk of one workgroup per CU; the CUs this leaves free run the workgroups past gemm_wgs, which do an independent small
+// operator (rvsa_sampling_body.h) and return.  NO workgroup waits on another: no flag, no spin loop, no atomic between riders and GEMM workgroups -- a
+// rider that starts late or runs long only lengthens the launch.
+struct P8RiderKArgs : KArgs {
+    P8Rider rider;
+};
+template <int RK> struct P8KArgs { typedef P8RiderKArgs type; };
+template <> struct P8KArgs<0> { typedef KArgs type; };
+
+template <typename Tout, int EPI, int MI1, int XP, int PS, int SP = 0, int RK = 0>
+__global__ __launch_bounds__(P8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_nt_p8_kernel(typename P8KArgs<RK>::type p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    if constexpr (RK != 0) {
+        if ((int)blockIdx.x >= p.rider.gemm_wgs) {
+            p8_rider_run<RK>(p.rider, (int)blockIdx.x - p.rider.gemm_wgs, smem);
+            return;
+        }
+    }
     constexpr int WROWS = 64 + 16 * MI1, BM = 2 * WROWS;      // rows per wave row, rows per tile
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -224,7 +281,8 @@ __global__ __launch_bounds__(P8_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 
         if constexpr (PS) {
             const int em0 = m0, en0 = n0;
-            tile += gridDim.x;
+            if constexpr (RK != 0) tile += p.rider.gemm_wgs;   // the stride of the walk is the number of GEMM workgroups
+            else tile += gridDim.x;
             const bool more = tile < ntiles;
             if (more) {   // the ring is idle: the next tile's first two K-tiles go out before this tile's stores
                 tile_coords(plain ? tile : xcd_remap(tile, ntiles), tiles_m, tiles_n, plain, tm, tn);
@@ -259,6 +317,19 @@ int launch_p8_kernel(const KArgs& a, int ntiles, hipStream_t stream) {
     const int cus = mtp_stream_cus(stream);
     const int grid = PS ? (ntiles < cus ? ntiles : cus) : ntiles;
     hipLaunchKernelGGL((gemm_nt_p8_kernel<Tout, EPI, MI1, XP, PS, SP>), dim3(grid), dim3(P8_THREADS), LDS, stream, a);
+    return mtp_launch_status();
+}
+
+// the two launches of the training step that carry riders: the persistent qkv forward (RK = 1) and the one-round qkv data gradient (RK = 2)
+template <int PS, int RK>
+int launch_p8_rider_kernel(const KArgs& k, const P8Rider& r, hipStream_t stream) {
+    constexpr int LDS = P8_LDS + 8 * 4096;
+    static unsigned long long optin = 0;
+    if (const int e = mtp_optin_lds((const void*)gemm_nt_p8_kernel<bf16_t, MTP_EPI_BIAS, 3, 0, PS, 1, RK>, LDS, optin)) return e;
+    P8RiderKArgs a;
+    static_cast<KArgs&>(a) = k;
+    a.rider = r;
+    hipLaunchKernelGGL((gemm_nt_p8_kernel<bf16_t, MTP_EPI_BIAS, 3, 0, PS, 1, RK>), dim3(r.gemm_wgs + r.riders), dim3(P8_THREADS), LDS, stream, a);
     return mtp_launch_status();
 }
 
@@ -313,6 +384,41 @@ int mtp_nt_p8_pick_tile_m(int64_t M, int64_t N, int64_t cus) {
     const int64_t t256 = mtp_nt_p8_tiles(M, N, 256), t224 = mtp_nt_p8_tiles(M, N, 224);
     const int64_t c256 = ((t256 + cus - 1) / cus) * 256, c224 = ((t224 + cus - 1) / cus) * 224;
     return c224 < c256 ? 224 : 256;
+}
+
+// GEMM workgroups of a launch that lends its idle CUs to riders: the fewest that finish `ntiles` in the same number of rounds as one per CU
+extern "C" int mtp_nt_p8_gemm_wgs(int ntiles, int cus) {
+    if (ntiles <= 0 || cus <= 0) return MTP_ERR_ARG;
+    const int rounds = (ntiles + cus - 1) / cus;
+    return (ntiles + rounds - 1) / rounds;
+}
+
+// MTP_ERR_UNSUPPORTED, with nothing launched, when this problem cannot carry the rider: no instantiation for the plan (bf16 out, bias epilogue, 224-row
+// tiles, nt stores; persistent under the forward rider, one round under the backward one), no spare CU, or scratch beyond the launch's LDS.
+// kind MTP_NT_RIDER_NONE: the even walk alone, no riders (the A/B of what giving up the uneven walk costs).
+int mtp_nt_p8_launch_rider(const KArgs& k, int out_dtype, int epi, const NtPlan& plan, int kind, const P8Rider& rider, hipStream_t stream) {
+    if (!mtp_nt_p8_fits(k, out_dtype, epi) || out_dtype != MTP_BF16 || epi != MTP_EPI_BIAS || plan.tile_m != 224 || plan.store_policy != 1) return MTP_ERR_UNSUPPORTED;
+    if ((kind == MTP_NT_RIDER_SAMPLING_BWD_WIN) == (plan.persistent != 0)) return MTP_ERR_UNSUPPORTED;
+    KArgs a = k;
+    a.tiles_n = (k.N + P8_BN - 1) / P8_BN;
+    a.k_tiles = k.K / 64;
+    a.order = plan.order;
+    a.atomic_out = 0;
+    const int ntiles = mtp_nt_p8_tiles(k.M, k.N, 224), cus = mtp_stream_cus(stream);
+    if (!plan.persistent && ntiles > cus) return MTP_ERR_UNSUPPORTED;      // several waves of one-tile workgroups: no CU is idle from the start
+    P8Rider r = rider;
+    r.gemm_wgs = plan.persistent ? mtp_nt_p8_gemm_wgs(ntiles, cus) : ntiles;
+    const int spare = cus - r.gemm_wgs;
+    r.riders = kind == MTP_NT_RIDER_NONE ? 0 : (spare < 32 ? spare : 32) < r.windows ? (spare < 32 ? spare : 32) : r.windows;
+    if (kind != MTP_NT_RIDER_NONE) {
+        if (r.riders <= 0) return MTP_ERR_UNSUPPORTED;
+        // scratch in the launch's LDS.  Forward: one pooled row of C floats per window of a rider, in whole groups of P8_RIDER_ROWS; backward: N floats + 4 KiB per half
+        const int64_t rows = ((r.windows + r.riders - 1) / r.riders + P8_RIDER_ROWS - 1) / P8_RIDER_ROWS * P8_RIDER_ROWS;
+        const int64_t scratch = kind == MTP_NT_RIDER_SAMPLING_FWD ? rows * 4 * (int64_t)r.C : 2 * (4096 + (((int64_t)r.N * 4 + 15) & ~15ll));
+        if (scratch > P8_LDS + 8 * 4096) return MTP_ERR_UNSUPPORTED;
+    }
+    if (kind == MTP_NT_RIDER_SAMPLING_BWD_WIN) return launch_p8_rider_kernel<0, 2>(a, r, stream);
+    return launch_p8_rider_kernel<1, 1>(a, r, stream);
 }
 
 int mtp_nt_p8_launch(const KArgs& k, int out_dtype, int epi, const NtPlan& plan, hipStream_t stream) {

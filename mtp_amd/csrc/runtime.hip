@@ -12,7 +12,9 @@
 // per-descriptor lr scale in a device table of its own).
 // mtp_gemm_nt_plan (the dispatch of mtp_gemm_nt as a query; mtp_gemm_nt_tile wraps it) and the enum mtp_gemm_variant naming the bits of mtp_gemm_args.variant at their
 // old values: no struct changed.
-extern "C" const char* mtp_version(void) { return "mtp_hip 0.6 (gfx950)"; }
+// 0.6.1: additive -- mtp_gemm_nt_rider with the new struct mtp_nt_rider (the NT GEMM with rider workgroups on the CUs its launch leaves idle) and the host query
+// mtp_nt_p8_gemm_wgs; no existing struct changed.
+extern "C" const char* mtp_version(void) { return "mtp_hip 0.6.1 (gfx950)"; }
 
 // A stream of the LOWEST priority the device offers (non-blocking), for work that is off the critical path and should only take the CUs
 // the main stream leaves idle: the grouped weight-gradient launches next to under-filled data-gradient GEMMs (engine_intern.py).

@@ -2,6 +2,7 @@
 // small f32 linear layer -- separately (rvsa_pool_*, small_linear_*) and as one launch each way per block (rvsa_sampling_*).
 // The window geometry is RvsaWindows (common.h), the one the attention kernels and the windowed LayerNorm backward use.
 #include "common.h"
+#include "rvsa_sampling_body.h"
 
 namespace {
 
@@ -256,68 +257,11 @@ __global__ __launch_bounds__(256) void rvsa_sampling_fwd_kernel(const T* __restr
                                                                float* __restrict__ avg, float* __restrict__ pooled, float* __restrict__ samp,
                                                                int Hp, int Wp, int C, int N, int pad_t, int pad_l, int nh, int nw) {
     extern __shared__ __attribute__((aligned(16))) float pl[];     // pooled row of this window
-    const int win = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int j = win % nw, i = (win / nw) % nh, b = win / (nw * nh);
-    for (int c4 = threadIdx.x; c4 < C / 4; c4 += 256) {
-        float4 s = make_float4(0, 0, 0, 0);
-#pragma unroll      // (round 4: all 49 row loads of the window in flight -- with `unroll 1` the seven rows were seven serialised round trips, most of the kernel's 17.6 us)
-        for (int a = 0; a < 7; ++a) {
-            const int y = i * 7 + a - pad_t;
-            const bool yok = y >= 0 && y < Hp;
-            const int yc = yok ? y : 0;
-            float4 v[7];
-#pragma unroll
-            for (int bb = 0; bb < 7; ++bb) {
-                const int xx = j * 7 + bb - pad_l;
-                const int xc = (xx >= 0 && xx < Wp) ? xx : 0;
-                v[bb] = load4(x + (((int64_t)b * Hp + yc) * Wp + xc) * C + 4 * c4);
-            }
-#pragma unroll
-            for (int bb = 0; bb < 7; ++bb) {
-                const int xx = j * 7 + bb - pad_l;
-                const float m = (yok && xx >= 0 && xx < Wp) ? 1.f : 0.f;
-                s.x += m * v[bb].x; s.y += m * v[bb].y; s.z += m * v[bb].z; s.w += m * v[bb].w;
-            }
-        }
-        const float inv = 1.0f / 49.0f;
-        s = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
-        const float4 p = make_float4(s.x > 0 ? s.x : 0.01f * s.x, s.y > 0 ? s.y : 0.01f * s.y, s.z > 0 ? s.z : 0.01f * s.z, s.w > 0 ? s.w : 0.01f * s.w);
-        if (blockIdx.y == 0) {
-            store4(avg + (int64_t)win * C + 4 * c4, s);
-            store4(pooled + (int64_t)win * C + 4 * c4, p);
-        }
-        *reinterpret_cast<float4*>(pl + 4 * c4) = p;
-    }
-    __syncthreads();
     // gridDim.y workgroups share a window: each pools it (the second reads come out of L2) and produces its share of the N outputs
     const int nper = ((N + (int)gridDim.y - 1) / (int)gridDim.y + 3) / 4 * 4, nlo = (int)blockIdx.y * nper, nhi = (nlo + nper) < N ? (nlo + nper) : N;
-    for (int n0 = nlo + 4 * wave; n0 < nhi; n0 += 16) {      // 4 output columns per pass
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        // 4 k-steps x 4 outputs = 16 weight loads of 16 B in flight per lane before the first use (round 6: written as one k-step per iteration the loop bound is a
-        // run-time value, hipcc kept the iterations apart and a pass was C / 256 dependent L2 round trips -- most of the kernel's 21.6 us at C = 1024)
-        for (int k0 = lane * 4; k0 < C; k0 += 1024) {
-            float4 ww[4][4], a[4];
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                const int k = k0 + 256 * kk, kc = k < C ? k : 0;
-                a[kk] = k < C ? *reinterpret_cast<const float4*>(pl + kc) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int n = n0 + q < N ? n0 + q : N - 1;
-                    ww[kk][q] = load4(w + (int64_t)n * C + kc);
-                }
-            }
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q] += a[kk].x * ww[kk][q].x + a[kk].y * ww[kk][q].y + a[kk].z * ww[kk][q].z + a[kk].w * ww[kk][q].w;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float t = wave_sum(acc[q]);
-            if (lane == 0 && n0 + q < nhi) samp[(int64_t)win * N + n0 + q] = t + (bias ? bias[n0 + q] : 0.f);
-        }
-    }
+    rvsa_pool_window<T>(x, avg, pooled, Hp, Wp, C, pad_t, pad_l, nh, nw, (int)blockIdx.x, blockIdx.y == 0, (int)threadIdx.x, pl);
+    __syncthreads();
+    rvsa_heads<1>(w, bias, samp, C, N, nlo, nhi, (int)threadIdx.x >> 6, 4, (int)threadIdx.x & 63, pl, (int)blockIdx.x, 0, (int)gridDim.x);
 }
 
 // workgroup = (window, 64 channel quads); its 4 waves split the N head outputs of the dsamp . w product (N / 4 dependent-free weight
@@ -378,32 +322,8 @@ __global__ __launch_bounds__(256) void rvsa_sampling_bwd_kernel(const float* __r
 __global__ __launch_bounds__(256) void rvsa_sampling_bwd_win_kernel(const float* __restrict__ dsamp, const float* __restrict__ w, const float* __restrict__ avg,
                                                                    float* __restrict__ g, int C, int N) {
     extern __shared__ __attribute__((aligned(16))) float ds[];     // dsamp row of this window
-    __shared__ float4 part[4][64];
-    const int win = blockIdx.x;
-    const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
-    const int c4 = blockIdx.y * 64 + lane;
-    const bool live = c4 < C / 4;
-    for (int n = threadIdx.x; n < N; n += 256) ds[n] = dsamp[(int64_t)win * N + n];
-    __syncthreads();
-    const int nq = (N + 3) / 4, n0 = q * nq, n1 = (n0 + nq) < N ? (n0 + nq) : N;
-    float4 d = make_float4(0, 0, 0, 0);
-    if (live) {
-#pragma unroll 10
-        for (int n = n0; n < n1; ++n) {
-            const float4 ww = load4(w + (int64_t)n * C + 4 * c4);
-            const float t = ds[n];
-            d.x += t * ww.x; d.y += t * ww.y; d.z += t * ww.z; d.w += t * ww.w;
-        }
-    }
-    part[q][lane] = d;
-    __syncthreads();
-    if (!live || q) return;
-    const float4 p0 = part[0][lane], p1 = part[1][lane], p2 = part[2][lane], p3 = part[3][lane];   // the order of rvsa_sampling_bwd_kernel: same bits
-    d = make_float4((p0.x + p1.x) + (p2.x + p3.x), (p0.y + p1.y) + (p2.y + p3.y), (p0.z + p1.z) + (p2.z + p3.z), (p0.w + p1.w) + (p2.w + p3.w));
-    const float4 a = load4(avg + (int64_t)win * C + 4 * c4);
-    const float k = 1.0f / 49.0f;
-    *reinterpret_cast<float4*>(g + (int64_t)win * C + 4 * c4) =
-        make_float4(d.x * (a.x > 0 ? k : 0.01f * k), d.y * (a.y > 0 ? k : 0.01f * k), d.z * (a.z > 0 ? k : 0.01f * k), d.w * (a.w > 0 ? k : 0.01f * k));
+    __shared__ float4 part[4 * 64];
+    rvsa_sampling_bwd_win_body(dsamp, w, avg, g, C, N, (int)blockIdx.x, (int)blockIdx.y * 64, true, (int)threadIdx.x, ds, part);
 }
 
 extern "C" int mtp_rvsa_sampling_bwd_win(const float* dsamp, const float* w, const float* avg, float* g, int64_t windows, int64_t C, int64_t N, mtp_stream_t stream) {

@@ -170,6 +170,12 @@ class BackboneEngine(EngineBase):
         s = torch.floor(keep + torch.rand(self.depth, 2, B, device=self.dev, dtype=F32)) / keep
         return [(s[i, 0], s[i, 1]) if live[i] else (None, None) for i in range(self.depth)]
 
+    @property
+    def _ride(self):
+        """the sampling heads of a window block ride inside the qkv GEMM launches (ops.gemm_nt(rider=...)) in the bf16 step; the f32 parity mode and the
+        recomputing forward of use_checkpoint keep the separate launches"""
+        return self.act == torch.bfloat16 and not self.m.use_checkpoint
+
     # ------------------------------------------------------------------ block forward
     def _block_fwd(self, i, x, B, Hp, Wp, dps, save):
         P, b, C, T, N = self.P, self._blk[i], self.C, x.shape[0], Hp * Wp
@@ -177,14 +183,19 @@ class BackboneEngine(EngineBase):
         s = {}
         mean1, rstd1 = self._e(T, dtype=F32), self._e(T, dtype=F32)
         ln1 = ops.layernorm_fwd(x, P[pre + "norm1.weight"], P[pre + "norm1.bias"], self._e(T, C), mean1, rstd1)
+        rider = None
         if b.window:
             # (the sampling heads on a second stream next to the qkv GEMM, joined by events: +0.25 ms per forward pass, round 4 -- the two cross-queue
             #  waits per block cost more than the 22 us they hide)
             nh, nw = ops.rvsa_windows(Hp, Wp)
             R = B * nh * nw
             avg, pooled = self._e(R, C, dtype=F32), self._e(R, C, dtype=F32)
-            samp = ops.rvsa_sampling_fwd(ln1, b.wsamp, b.bsamp, avg, pooled, self._e(R, 5 * self.heads, dtype=F32), B, Hp, Wp)
-        qkv = ops.gemm_nt(ln1, b.wqkv, self._e(T, 3 * C), bias=P[pre + "attn.qkv.bias"])
+            samp = self._e(R, 5 * self.heads, dtype=F32)
+            if self._ride:    # inside the qkv launch, on the CUs it leaves idle
+                rider = ops.sampling_fwd_rider(ln1, b.wsamp, b.bsamp, avg, pooled, samp, B, Hp, Wp)
+            else:
+                ops.rvsa_sampling_fwd(ln1, b.wsamp, b.bsamp, avg, pooled, samp, B, Hp, Wp)
+        qkv = ops.gemm_nt(ln1, b.wqkv, self._e(T, 3 * C), bias=P[pre + "attn.qkv.bias"], rider=rider)
         o = self._e(T, C)
         if b.window:
             lse = self._e(R * self.heads * 49, dtype=F32)
@@ -266,12 +277,16 @@ class BackboneEngine(EngineBase):
             ops.full_attn_bwd(s["qkv"], s["o"], do, s["lse"], dqkv, rel_h, rel_w, drel_h, drel_w, B, Hp, Wp, self.heads, self.scale,
                               accumulate=True, defer=self._ln_parts)
         wq.add(dqkv, s["ln1"], G[pre + "attn.qkv.weight"], G[pre + "attn.qkv.bias"])
-        win_add = None
+        win_add = rider = None
         if b.window:
             # dln1 += pool'(linear'(dsamp)): the per-window factor (windows, C) is one small launch; norm1's backward adds it to every token
             # row of the window while it reads the row anyway (round 4: was a read-modify-write pass over (T, C), 17 us per block).
-            win_add = ops.rvsa_sampling_bwd_win(dsamp, b.wsamp, s["avg"], self._e(*s["avg"].shape, dtype=F32))
-        dln1 = ops.gemm_nt(dqkv, b.wqkvT, self._e(T, C))
+            win_add = self._e(*s["avg"].shape, dtype=F32)
+            if self._ride:    # inside the qkv data-gradient launch
+                rider = ops.sampling_bwd_win_rider(dsamp, b.wsamp, s["avg"], win_add)
+            else:
+                ops.rvsa_sampling_bwd_win(dsamp, b.wsamp, s["avg"], win_add)
+        dln1 = ops.gemm_nt(dqkv, b.wqkvT, self._e(T, C), rider=rider)
         dx0, dx0_act = self._e(T, C, dtype=F32), self._e(T, C)
         self._ln_bwd(dln1, s["x"], s["mean1"], s["rstd1"], P[pre + "norm1.weight"], dx0, G[pre + "norm1.weight"], G[pre + "norm1.bias"],
                           dres=dx1, extra=extra, dx_copy=dx0_act, copy_scale=prev_scale, rows_per_sample=N,

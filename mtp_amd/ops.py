@@ -79,11 +79,29 @@ def _nt_args(a, w, out, epi, bias, bias_mod, res, res_mod, rowscale, rows_per_sa
     return g
 
 
+def sampling_fwd_rider(x, w, b, avg, pooled, samp, B, Hp, Wp):
+    """rvsa_sampling_fwd(...) as a rider of gemm_nt: the same arguments, the same results"""
+    r = _lib.NtRider(kind=_lib.NT_RIDER_SAMPLING_FWD, act_dtype=_dt(x), x=_p(x), w=_f32(w), bias=_f32(b), avg=_f32(avg), pooled=_f32(pooled), samp=_f32(samp),
+                     B=B, Hp=Hp, Wp=Wp, C=x.shape[-1], N=w.shape[0])
+    return r
+
+
+def sampling_bwd_win_rider(dsamp, w, avg, g):
+    """rvsa_sampling_bwd_win(...) as a rider of gemm_nt"""
+    r = _lib.NtRider(kind=_lib.NT_RIDER_SAMPLING_BWD_WIN, act_dtype=MTP_BF16, dsamp=_f32(dsamp), w=_f32(w), avg=_f32(avg), g=_f32(g),
+                     windows=avg.shape[0], C=avg.shape[1], N=w.shape[0])
+    return r
+
+
 def gemm_nt(a, w, out, epi=EPI_BIAS, bias=None, bias_mod=0, res=None, res_mod=0, rowscale=None, rows_per_sample=0,
-            aux=None, variant=0, n=None):
-    """out (M,N) = epilogue(a (M,K) @ w (N,K)^T)."""
+            aux=None, variant=0, n=None, rider=None):
+    """out (M,N) = epilogue(a (M,K) @ w (N,K)^T).  rider (sampling_fwd_rider / sampling_bwd_win_rider): an independent small operator that runs inside the
+    same launch on the CUs the GEMM leaves idle (mtp_gemm_nt_rider), or right behind the GEMM where the launch has none to lend."""
     g = _nt_args(a, w, out, epi, bias, bias_mod, res, res_mod, rowscale, rows_per_sample, aux, variant, n)
-    check(lib().mtp_gemm_nt(C.byref(g), _s()), "mtp_gemm_nt")
+    if rider is not None:
+        check(lib().mtp_gemm_nt_rider(C.byref(g), C.byref(rider), _s()), "mtp_gemm_nt_rider")
+    else:
+        check(lib().mtp_gemm_nt(C.byref(g), _s()), "mtp_gemm_nt")
     return out
 
 
