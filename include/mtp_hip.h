@@ -167,6 +167,33 @@ struct mtp_nt_rider {
     int64_t C, N;
 };
 int mtp_gemm_nt_rider(const mtp_gemm_args* args, const struct mtp_nt_rider* rider, mtp_stream_t stream);
+/* Query, no launch: what mtp_gemm_nt_rider does with these arguments on a stream of `cus` compute units (cus <= 0: the device's; 256 when there is none) --
+ * one launch with rider workgroups, or the two launches one after the other and why.  mtp_gemm_nt_rider decides through the same function; with cus > 0
+ * no device is touched.  Same argument checks and return codes as mtp_gemm_nt_rider.
+ *   rides              1 = one launch of the rider instantiation (under MTP_NT_RIDER_NONE, on a persistent plan: the even walk alone, riders = 0); 0 = GEMM, then the stand-alone kernel
+ *   gemm_wgs           workgroups that walk the GEMM's tiles (also the stride of the walk); the launch has gemm_wgs + riders workgroups
+ *   riders             min(spare CUs, 32, windows)
+ *   windows_per_rider  ceil(windows / riders): every trip count of a rider follows from it
+ *   scratch_bytes      LDS a rider workgroup uses.  Forward: 4 C bytes per pooled row, rows = windows_per_rider rounded up to whole groups of 4;
+ *                      backward: 2 x (4096 + 4 N rounded up to 16).  At most the launch's 160 KiB
+ *   reason             MTP_NT_RIDE_OK, or why not.  NO_FAMILY / NO_INSTANTIATION leave the other fields 0, NO_SPARE_CU fills gemm_wgs (0 where a one-round plan has
+ *                      more tiles than CUs), NO_SCRATCH fills everything (scratch_bytes is what would have been needed). */
+enum {
+    MTP_NT_RIDE_OK = 0,
+    MTP_NT_RIDE_NO_FAMILY = 1,          /* the plan (mtp_gemm_nt_plan) is not the P8 family */
+    MTP_NT_RIDE_NO_INSTANTIATION = 2,   /* P8, but not bf16 out / bias epilogue / 224-row tiles / nt stores, or not persistent under the forward rider, persistent under the backward one */
+    MTP_NT_RIDE_NO_SPARE_CU = 3,        /* every CU of the stream has a GEMM workgroup (or a one-round plan has more tiles than CUs) */
+    MTP_NT_RIDE_NO_SCRATCH = 4          /* the rider's scratch exceeds the launch's LDS */
+};
+struct mtp_nt_rider_plan {
+    int rides;
+    int gemm_wgs;
+    int riders;
+    int windows_per_rider;
+    int scratch_bytes;
+    int reason;           /* MTP_NT_RIDE_* */
+};
+int mtp_gemm_nt_rider_plan(const mtp_gemm_args* args, const struct mtp_nt_rider* rider, int cus, struct mtp_nt_rider_plan* out);
 /* GEMM workgroups of a P8 launch of `ntiles` tiles that carries riders on `cus` compute units: the fewest that still finish in ceil(ntiles / cus) rounds
  * (the other cus - result CUs are spare).  Host arithmetic, no device needed; MTP_ERR_ARG unless both are positive. */
 int mtp_nt_p8_gemm_wgs(int ntiles, int cus);

@@ -67,6 +67,15 @@ class NtRider(C.Structure):
                 ("B", i64), ("Hp", i64), ("Wp", i64), ("windows", i64), ("C", i64), ("N", i64)]
 
 
+# reasons of struct mtp_nt_rider_plan (mtp_gemm_nt_rider_plan)
+NT_RIDE_OK, NT_RIDE_NO_FAMILY, NT_RIDE_NO_INSTANTIATION, NT_RIDE_NO_SPARE_CU, NT_RIDE_NO_SCRATCH = 0, 1, 2, 3, 4
+
+
+class NtRiderPlan(C.Structure):
+    """struct mtp_nt_rider_plan"""
+    _fields_ = [("rides", i32), ("gemm_wgs", i32), ("riders", i32), ("windows_per_rider", i32), ("scratch_bytes", i32), ("reason", i32)]
+
+
 class WimgDesc(C.Structure):
     """mtp_wimg_desc"""
     _fields_ = [("src", p), ("w", p), ("wt", p), ("R", i64), ("C", i64), ("tile0", i64), ("f32_out", C.c_int32), ("wd", C.c_float)]
@@ -98,6 +107,7 @@ SIGNATURES = {
     "mtp_gemm_nt_tile": (i32, [C.POINTER(GemmArgs)]),
     "mtp_gemm_nt_workspace_bytes": (i64, []),
     "mtp_gemm_nt_rider": (i32, [C.POINTER(GemmArgs), C.POINTER(NtRider), p]),
+    "mtp_gemm_nt_rider_plan": (i32, [C.POINTER(GemmArgs), C.POINTER(NtRider), i32, C.POINTER(NtRiderPlan)]),
     "mtp_nt_p8_gemm_wgs": (i32, [i32, i32]),
     "mtp_gemm_tn": (i32, [C.POINTER(GemmArgs), p]),
     "mtp_gemm_tn_grouped": (i32, [C.POINTER(GemmArgs), i32, p]),

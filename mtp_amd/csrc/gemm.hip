@@ -740,11 +740,10 @@ extern "C" int mtp_gemm_nt(const mtp_gemm_args* a, mtp_stream_t stream) {
     return MTP_ERR_UNSUPPORTED;
 }
 
-// The GEMM with a rider (include/mtp_hip.h).  Every argument check precedes the first launch; a problem that cannot carry the rider falls back to the two
-// launches it replaces, in the order GEMM, stand-alone kernel.
-extern "C" int mtp_gemm_nt_rider(const mtp_gemm_args* a, const struct mtp_nt_rider* r, mtp_stream_t stream) {
-    if (!a || !r) return MTP_ERR_ARG;
-    P8Rider k8{};
+namespace {
+// the rider's own argument checks, and its pointers and sizes as the kernel takes them
+int rider_args(const struct mtp_nt_rider* r, P8Rider& k8) {
+    k8 = P8Rider{};
     if (r->kind == MTP_NT_RIDER_SAMPLING_FWD) {      // the checks of mtp_rvsa_sampling_fwd
         if (!r->x || !r->w || !r->avg || !r->pooled || !r->samp || r->B <= 0 || r->Hp <= 0 || r->Wp <= 0 || r->C <= 0 || (r->C % 4) || r->C > 8192 || r->N <= 0) return MTP_ERR_ARG;
         if (r->act_dtype != MTP_BF16) return MTP_ERR_UNSUPPORTED;
@@ -760,20 +759,54 @@ extern "C" int mtp_gemm_nt_rider(const mtp_gemm_args* a, const struct mtp_nt_rid
     }
     k8.C = (int)r->C; k8.N = (int)r->N;
     k8.x = r->x; k8.dsamp = r->dsamp; k8.w = r->w; k8.bias = r->bias; k8.avg = r->avg; k8.pooled = r->pooled; k8.samp = r->samp; k8.g = r->g;
+    return 0;
+}
+// a GEMM that can carry a rider at all (bf16 in and out, bias epilogue): its own argument checks, kernel arguments and plan on `cus` CUs.
+// 1 = k and plan are filled, 0 = another kind of GEMM (nothing filled), < 0 = a refused argument
+int rider_gemm(const mtp_gemm_args* a, int cus, KArgs& k, NtPlan& plan) {
+    if (a->in_dtype != MTP_BF16 || a->out_dtype != MTP_BF16 || a->epilogue != MTP_EPI_BIAS) return 0;
+    if (const int rc = fill_common<bf16_t>(a, k)) return rc;
+    if ((a->K % Elem<bf16_t>::kPerChunk) || (a->bias && a->bias_mod > 0 && (a->bias_mod % 4))) return MTP_ERR_ARG;
+    plan = nt_plan(a, k, cus);
+    return 1;
+}
+}  // namespace
+
+// The GEMM with a rider (include/mtp_hip.h).  Every argument check precedes the first launch; a problem that cannot carry the rider falls back to the two
+// launches it replaces, in the order GEMM, stand-alone kernel.
+extern "C" int mtp_gemm_nt_rider(const mtp_gemm_args* a, const struct mtp_nt_rider* r, mtp_stream_t stream) {
+    if (!a || !r) return MTP_ERR_ARG;
+    P8Rider k8;
+    if (const int rc = rider_args(r, k8)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (a->in_dtype == MTP_BF16 && a->out_dtype == MTP_BF16 && a->epilogue == MTP_EPI_BIAS) {
-        KArgs k;
-        if (const int rc = fill_common<bf16_t>(a, k)) return rc;
-        if ((a->K % Elem<bf16_t>::kPerChunk) || (a->bias && a->bias_mod > 0 && (a->bias_mod % 4))) return MTP_ERR_ARG;
-        const NtPlan plan = nt_plan(a, k, mtp_stream_cus(s));
-        if (plan.family == MTP_GEMM_NT_FAMILY_P8) {
-            const int rc = mtp_nt_p8_launch_rider(k, a->out_dtype, a->epilogue, plan, r->kind, k8, s);
-            if (rc != MTP_ERR_UNSUPPORTED) return rc;
-        }
+    KArgs k;
+    NtPlan plan;
+    const int can = rider_gemm(a, mtp_stream_cus(s), k, plan);
+    if (can < 0) return can;
+    if (can && plan.family == MTP_GEMM_NT_FAMILY_P8) {
+        // the decision mtp_gemm_nt_rider_plan reports.  Behind a plan that rides there is no fallback: whatever the launch answers is the answer
+        const struct mtp_nt_rider_plan rp = mtp_nt_p8_rider_plan(k, a->out_dtype, a->epilogue, plan, r->kind, k8.windows, k8.C, k8.N, mtp_stream_cus(s));
+        if (rp.rides) return mtp_nt_p8_launch_rider(k, plan, r->kind, k8, rp, s);
     }
     if (const int rc = mtp_gemm_nt(a, stream)) return rc;
     if (r->kind == MTP_NT_RIDER_SAMPLING_FWD) return mtp_rvsa_sampling_fwd(r->x, r->act_dtype, r->w, r->bias, r->avg, r->pooled, r->samp, r->B, r->Hp, r->Wp, r->C, r->N, stream);
     if (r->kind == MTP_NT_RIDER_SAMPLING_BWD_WIN) return mtp_rvsa_sampling_bwd_win(r->dsamp, r->w, r->avg, r->g, r->windows, r->C, r->N, stream);
+    return 0;
+}
+
+// What mtp_gemm_nt_rider does with these arguments on `cus` CUs, without launching: the same checks, the same plan, the same decision function.
+extern "C" int mtp_gemm_nt_rider_plan(const mtp_gemm_args* a, const struct mtp_nt_rider* r, int cus, struct mtp_nt_rider_plan* out) {
+    if (!a || !r || !out) return MTP_ERR_ARG;
+    P8Rider k8;
+    if (const int rc = rider_args(r, k8)) return rc;
+    if (cus <= 0) cus = mtp_stream_cus(nullptr);
+    KArgs k;
+    NtPlan plan;
+    const int can = rider_gemm(a, cus, k, plan);
+    if (can < 0) return can;
+    if (!can && mtp_gemm_nt_plan(a, cus, &plan)) return MTP_ERR_ARG;      // (a GEMM of another dtype or epilogue: its plan only names the reason)
+    const struct mtp_nt_rider_plan none = {0, 0, 0, 0, 0, plan.family == MTP_GEMM_NT_FAMILY_P8 ? MTP_NT_RIDE_NO_INSTANTIATION : MTP_NT_RIDE_NO_FAMILY};
+    *out = can && plan.family == MTP_GEMM_NT_FAMILY_P8 ? mtp_nt_p8_rider_plan(k, a->out_dtype, a->epilogue, plan, r->kind, k8.windows, k8.C, k8.N, cus) : none;
     return 0;
 }
 

@@ -50,9 +50,12 @@ int mtp_nt_p8_launch(const KArgs& k, int out_dtype, int epilogue, const NtPlan& 
 int mtp_nt_p8_fits(const KArgs& k, int out_dtype, int epilogue);   // 1 when mtp_nt_p8_launch would run the problem
 int mtp_nt_p8_tiles(int64_t M, int64_t N, int tile_m);             // tiles of tile_m rows the kernel cuts an (M, N) output into
 int mtp_nt_p8_pick_tile_m(int64_t M, int64_t N, int64_t cus);      // the cheaper of 256- and 224-row tiles on `cus` CUs
-// the same launch with up to 32 rider workgroups on the CUs the GEMM leaves idle (kind: MTP_NT_RIDER_*; rider.gemm_wgs / riders are filled here).
-// MTP_ERR_UNSUPPORTED, nothing launched, when the problem cannot carry the rider: the caller launches the two kernels one after the other.
-int mtp_nt_p8_launch_rider(const KArgs& k, int out_dtype, int epilogue, const NtPlan& plan, int kind, const P8Rider& rider, hipStream_t stream);
+// the same launch with up to 32 rider workgroups on the CUs the GEMM leaves idle (kind: MTP_NT_RIDER_*).  Whether a problem carries the rider on a stream of
+// `cus` CUs, and how the launch is split, is decided in ONE function (host arithmetic, no device) that the entry point and the query mtp_gemm_nt_rider_plan
+// both call; windows / C / N: the rider's sizes (P8Rider).  The launcher runs a plan that rides (rider.gemm_wgs / riders are filled from it) and decides nothing:
+// where the plan does not ride, the caller launches the two kernels one after the other.
+struct mtp_nt_rider_plan mtp_nt_p8_rider_plan(const KArgs& k, int out_dtype, int epilogue, const NtPlan& plan, int kind, int windows, int C, int N, int cus);
+int mtp_nt_p8_launch_rider(const KArgs& k, const NtPlan& plan, int kind, const P8Rider& rider, const struct mtp_nt_rider_plan& rp, hipStream_t stream);
 // gemm_s8.hip: 128 x 256 x 64 strips, 8 waves, two accumulator sets: the epilogue of a strip runs under the next strip's K loop
 // (bf16 NT, K >= 704 in whole K-tiles).  order: 1 = plain strip order.  MTP_ERR_UNSUPPORTED when the problem does not fit.
 int mtp_nt_s8_launch(const KArgs& k, int out_dtype, int epilogue, int order, hipStream_t stream);

@@ -393,30 +393,49 @@ extern "C" int mtp_nt_p8_gemm_wgs(int ntiles, int cus) {
     return (ntiles + rounds - 1) / rounds;
 }
 
-// MTP_ERR_UNSUPPORTED, with nothing launched, when this problem cannot carry the rider: no instantiation for the plan (bf16 out, bias epilogue, 224-row
-// tiles, nt stores; persistent under the forward rider, one round under the backward one), no spare CU, or scratch beyond the launch's LDS.
-// kind MTP_NT_RIDER_NONE: the even walk alone, no riders (the A/B of what giving up the uneven walk costs).
-int mtp_nt_p8_launch_rider(const KArgs& k, int out_dtype, int epi, const NtPlan& plan, int kind, const P8Rider& rider, hipStream_t stream) {
-    if (!mtp_nt_p8_fits(k, out_dtype, epi) || out_dtype != MTP_BF16 || epi != MTP_EPI_BIAS || plan.tile_m != 224 || plan.store_policy != 1) return MTP_ERR_UNSUPPORTED;
-    if ((kind == MTP_NT_RIDER_SAMPLING_BWD_WIN) == (plan.persistent != 0)) return MTP_ERR_UNSUPPORTED;
+// Whether a P8 problem carries the rider on a stream of `cus` CUs, and how the launch is split (struct mtp_nt_rider_plan, include/mtp_hip.h).  It does not
+// when there is no instantiation for the plan (bf16 out, bias epilogue, 224-row tiles, nt stores; persistent under the forward rider, one round under
+// the backward one), no spare CU, or scratch beyond the launch's LDS.  kind MTP_NT_RIDER_NONE: the even walk alone, no riders (the A/B of what giving up
+// the uneven walk costs).  A wrong turn here is a silent slowdown (the fallback gives the same bits): tests/test_gemm_riders_host.py pins the decisions.
+struct mtp_nt_rider_plan mtp_nt_p8_rider_plan(const KArgs& k, int out_dtype, int epi, const NtPlan& plan, int kind, int windows, int C, int N, int cus) {
+    struct mtp_nt_rider_plan rp = {0, 0, 0, 0, 0, MTP_NT_RIDE_NO_INSTANTIATION};
+    if (!mtp_nt_p8_fits(k, out_dtype, epi) || out_dtype != MTP_BF16 || epi != MTP_EPI_BIAS || plan.tile_m != 224 || plan.store_policy != 1) return rp;
+    if ((kind == MTP_NT_RIDER_SAMPLING_BWD_WIN) == (plan.persistent != 0)) return rp;
+    const int ntiles = mtp_nt_p8_tiles(k.M, k.N, 224);
+    rp.reason = MTP_NT_RIDE_NO_SPARE_CU;
+    if (!plan.persistent && ntiles > cus) return rp;      // several waves of one-tile workgroups: no CU is idle from the start
+    rp.gemm_wgs = plan.persistent ? mtp_nt_p8_gemm_wgs(ntiles, cus) : ntiles;
+    if (kind != MTP_NT_RIDER_NONE) {
+        const int spare = cus - rp.gemm_wgs, lend = spare < 32 ? spare : 32;
+        rp.riders = lend < windows ? lend : windows;
+        if (rp.riders <= 0) {
+            rp.riders = 0;
+            return rp;
+        }
+        rp.windows_per_rider = (windows + rp.riders - 1) / rp.riders;
+        // scratch in the launch's LDS.  Forward: one pooled row of C floats per window of a rider, in whole groups of P8_RIDER_ROWS; backward: N floats + 4 KiB per half
+        const int64_t rows = (rp.windows_per_rider + P8_RIDER_ROWS - 1) / P8_RIDER_ROWS * P8_RIDER_ROWS;
+        const int64_t scratch = kind == MTP_NT_RIDER_SAMPLING_FWD ? rows * 4 * (int64_t)C : 2 * (4096 + (((int64_t)N * 4 + 15) & ~15ll));
+        rp.scratch_bytes = (int)(scratch < INT32_MAX ? scratch : INT32_MAX);
+        rp.reason = MTP_NT_RIDE_NO_SCRATCH;
+        if (scratch > P8_LDS + 8 * 4096) return rp;
+    }
+    rp.rides = 1;
+    rp.reason = MTP_NT_RIDE_OK;
+    return rp;
+}
+
+// launches what mtp_nt_p8_rider_plan decided for this stream (rp.rides).  The decision is the caller's: nothing here falls back
+int mtp_nt_p8_launch_rider(const KArgs& k, const NtPlan& plan, int kind, const P8Rider& rider, const struct mtp_nt_rider_plan& rp, hipStream_t stream) {
+    if (!rp.rides) return MTP_ERR_ARG;
     KArgs a = k;
     a.tiles_n = (k.N + P8_BN - 1) / P8_BN;
     a.k_tiles = k.K / 64;
     a.order = plan.order;
     a.atomic_out = 0;
-    const int ntiles = mtp_nt_p8_tiles(k.M, k.N, 224), cus = mtp_stream_cus(stream);
-    if (!plan.persistent && ntiles > cus) return MTP_ERR_UNSUPPORTED;      // several waves of one-tile workgroups: no CU is idle from the start
     P8Rider r = rider;
-    r.gemm_wgs = plan.persistent ? mtp_nt_p8_gemm_wgs(ntiles, cus) : ntiles;
-    const int spare = cus - r.gemm_wgs;
-    r.riders = kind == MTP_NT_RIDER_NONE ? 0 : (spare < 32 ? spare : 32) < r.windows ? (spare < 32 ? spare : 32) : r.windows;
-    if (kind != MTP_NT_RIDER_NONE) {
-        if (r.riders <= 0) return MTP_ERR_UNSUPPORTED;
-        // scratch in the launch's LDS.  Forward: one pooled row of C floats per window of a rider, in whole groups of P8_RIDER_ROWS; backward: N floats + 4 KiB per half
-        const int64_t rows = ((r.windows + r.riders - 1) / r.riders + P8_RIDER_ROWS - 1) / P8_RIDER_ROWS * P8_RIDER_ROWS;
-        const int64_t scratch = kind == MTP_NT_RIDER_SAMPLING_FWD ? rows * 4 * (int64_t)r.C : 2 * (4096 + (((int64_t)r.N * 4 + 15) & ~15ll));
-        if (scratch > P8_LDS + 8 * 4096) return MTP_ERR_UNSUPPORTED;
-    }
+    r.gemm_wgs = rp.gemm_wgs;
+    r.riders = rp.riders;
     if (kind == MTP_NT_RIDER_SAMPLING_BWD_WIN) return launch_p8_rider_kernel<0, 2>(a, r, stream);
     return launch_p8_rider_kernel<1, 1>(a, r, stream);
 }

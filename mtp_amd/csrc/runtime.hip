@@ -14,7 +14,8 @@
 // old values: no struct changed.
 // 0.6.1: additive -- mtp_gemm_nt_rider with the new struct mtp_nt_rider (the NT GEMM with rider workgroups on the CUs its launch leaves idle) and the host query
 // mtp_nt_p8_gemm_wgs; no existing struct changed.
-extern "C" const char* mtp_version(void) { return "mtp_hip 0.6.1 (gfx950)"; }
+// 0.6.2: additive -- mtp_gemm_nt_rider_plan with the new struct mtp_nt_rider_plan (what mtp_gemm_nt_rider decides, as a query); no existing struct changed.
+extern "C" const char* mtp_version(void) { return "mtp_hip 0.6.2 (gfx950)"; }
 
 // A stream of the LOWEST priority the device offers (non-blocking), for work that is off the critical path and should only take the CUs
 // the main stream leaves idle: the grouped weight-gradient launches next to under-filled data-gradient GEMMs (engine_intern.py).

@@ -105,6 +105,16 @@ def gemm_nt(a, w, out, epi=EPI_BIAS, bias=None, bias_mod=0, res=None, res_mod=0,
     return out
 
 
+def gemm_nt_rider_plan(a, w, out, rider, epi=EPI_BIAS, bias=None, bias_mod=0, res=None, res_mod=0, rowscale=None, rows_per_sample=0,
+                       aux=None, variant=0, n=None, cus=0):
+    """what gemm_nt(..., rider=rider) does on a stream of `cus` CUs (0: the device's; a CU-masked stream: the CUs of its mask), no launch: a
+    _lib.NtRiderPlan (rides, gemm_wgs, riders, windows_per_rider, scratch_bytes, reason = NT_RIDE_*)"""
+    g = _nt_args(a, w, out, epi, bias, bias_mod, res, res_mod, rowscale, rows_per_sample, aux, variant, n)
+    plan = _lib.NtRiderPlan()
+    check(lib().mtp_gemm_nt_rider_plan(C.byref(g), C.byref(rider), cus, C.byref(plan)), "mtp_gemm_nt_rider_plan")
+    return plan
+
+
 def gemm_nt_tile(a, w, out, epi=EPI_BIAS, bias=None, bias_mod=0, res=None, res_mod=0, rowscale=None, rows_per_sample=0,
                  aux=None, variant=0, n=None):
     """tile width (256 / 128; 64 = the strip kernel) of the kernel family gemm_nt(...) runs these arguments on (no launch)"""

@@ -214,6 +214,7 @@ _DTYPE_REFUSALS = {
 _DTYPE_IN_STRUCT = {
     "mtp_gemm_nt": "mtp_gemm_args.in_dtype / out_dtype", "mtp_gemm_tn": "mtp_gemm_args", "mtp_gemm_tn_grouped": "mtp_gemm_args",
     "mtp_gemm_nt_plan": "mtp_gemm_args", "mtp_gemm_nt_workspace_bytes": "mtp_gemm_args",
+    "mtp_gemm_nt_rider": "mtp_gemm_args, mtp_nt_rider.act_dtype", "mtp_gemm_nt_rider_plan": "mtp_gemm_args, mtp_nt_rider.act_dtype",
 }
 # a query with its own contract (the test above pins it): an unsupported dtype is the family NONE, and a query launches nothing
 _DTYPE_QUERY_NONE = "mtp_conv_kernel"
