@@ -715,6 +715,46 @@ int mtp_max_iou_assign(const float* gts, const float* priors, const int64_t* gt_
                        float neg_iou_lo, float neg_iou_hi, float min_pos_iou, int match_low_quality, int gt_max_assign_all, int64_t* gt_inds,
                        float* max_overlaps, int64_t* labels, void* workspace, int64_t workspace_bytes, mtp_stream_t stream);
 
+/* ---- the oriented RPN (csrc/rpn.hip): anchors, the midpoint-offset coder (mmrotate's MidpointOffsetCoder, 'le90'), targets + loss, proposals.
+ * f32 boxes and logits, int64 indices; no float atomics, two calls on the same inputs give the same bits.  The maps of a level are addressed by
+ * element strides (image, channel, y, x): cls channel a, reg channel a * 6 + j for anchor a of A.  The levels tile the flat multi-level anchor
+ * order (level, y, x, a) in the order given. ---- */
+#define MTP_RPN_MAX_LEVELS 8
+typedef struct mtp_rpn_level {
+    const float* cls;      /* logits */
+    const float* reg;      /* the six deltas */
+    float* dcls;           /* their gradients in the same strides, zeroed by the caller; all NULL (on every level): no gradients */
+    float* dreg;
+    int64_t H, W;
+    int64_t keep_count;    /* mtp_rpn_proposals: kept anchors of the level per image */
+    int64_t cls_stride[4], reg_stride[4];
+} mtp_rpn_level;
+/* priors (H W A, 4) x1 y1 x2 y2: prior (y W + x) A + a = base_anchors[a] + (x stride_w, y stride_h, x stride_w, y stride_h); inside_flags (H W A)
+ * bytes: x < min(ceil(pad_w / stride_w), W), the same for y, and, when allowed_border >= 0, x1 >= -b, y1 >= -b, x2 < img_w + b, y2 < img_h + b.
+ * base_anchors (A, 4) on the device; base_anchors and priors 16-byte aligned. */
+int mtp_rpn_anchors(const float* base_anchors, int64_t A, int64_t H, int64_t W, int64_t stride_w, int64_t stride_h, int64_t pad_h, int64_t pad_w,
+                    int64_t img_h, int64_t img_w, float allowed_border, float* priors, uint8_t* inside_flags, mtp_stream_t stream);
+int64_t mtp_rpn_loss_workspace_bytes(int64_t images, int64_t samples);
+/* Targets and loss of the whole batch, forward and backward, two launches.  priors (num_priors, 4): the flat multi-level priors; gts (K, 5): the
+ * rotated gt boxes of all images; samples (images, S): per image n_pos positives, then n_neg negatives (flat anchor indices, distinct within an
+ * image; the rest of the row is ignored); sample_gt (images, S): on positives the row of gts; n_pos, n_neg (images) on the device.  Per sample the
+ * sigmoid BCE of the logit against 1 / 0 and, on positives, SmoothL1(beta) of the six deltas against the encode of (prior, gt); loss_cls /
+ * loss_bbox (num_levels) = weight * (sum over the level) / avg_factor, avg_factor = sum (n_pos + n_neg); the gradients of their total are stored
+ * at the sampled anchors.  means, stds: 6 HOST floats each.  workspace: mtp_rpn_loss_workspace_bytes(images, S). */
+int mtp_rpn_loss(const mtp_rpn_level* levels, int num_levels, int64_t A, const float* priors, int64_t num_priors, const float* gts, int64_t K,
+                 const int64_t* samples, const int64_t* sample_gt, const int64_t* n_pos, const int64_t* n_neg, int64_t images, int64_t S,
+                 const float* means, const float* stds, float beta, float cls_weight, float bbox_weight, float* loss_cls, float* loss_bbox,
+                 void* workspace, int64_t workspace_bytes, mtp_stream_t stream);
+/* keep (images, T), T = sum keep_count, level after level: indices into the level's own H W A anchors.  Per entry: scores = sigmoid(logit), rboxes
+ * (., 5) = decode (cx, cy, w, h, theta; w >= h, theta in [-pi/2, pi/2)), hboxes (., 4) its circumscribed box (16-byte aligned), level_ids,
+ * valid = w > min_bbox_size && h > min_bbox_size.  One launch. */
+int mtp_rpn_proposals(const mtp_rpn_level* levels, int num_levels, int64_t A, const float* priors, int64_t num_priors, const int64_t* keep,
+                      int64_t images, const float* means, const float* stds, float min_bbox_size, float* scores, float* rboxes, float* hboxes,
+                      int64_t* level_ids, uint8_t* valid, mtp_stream_t stream);
+/* the coder on plain arrays: priors (n, 4), gts (n, 5) -> deltas (n, 6); priors (n, 4), deltas (n, 6) -> rboxes (n, 5) */
+int mtp_rpn_encode(const float* priors, const float* gts, const float* means, const float* stds, int64_t n, float* deltas, mtp_stream_t stream);
+int mtp_rpn_decode(const float* priors, const float* deltas, const float* means, const float* stds, int64_t n, float* rboxes, mtp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

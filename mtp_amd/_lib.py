@@ -88,6 +88,14 @@ class Dcnv3Geom(C.Structure):
                 ("group_channels", C.c_int32), ("offset_scale", C.c_float), ("im2col_step", C.c_int32), ("remove_center", C.c_int32), ("variant", C.c_int32)]
 
 
+RPN_MAX_LEVELS = 8
+
+
+class RpnLevel(C.Structure):
+    """struct mtp_rpn_level"""
+    _fields_ = [("cls", p), ("reg", p), ("dcls", p), ("dreg", p), ("H", i64), ("W", i64), ("keep_count", i64), ("cls_stride", i64 * 4), ("reg_stride", i64 * 4)]
+
+
 # name -> (restype, argtypes); must list EVERY function declared in include/mtp_hip.h (tests/test_abi.py checks)
 SIGNATURES = {
     "mtp_weight_images": (i32, [p, i32, i64, i32, p]),
@@ -214,6 +222,12 @@ SIGNATURES = {
     "mtp_nms_mask": (i32, [p, p, i64, i32, f32, p, i64, p]),
     "mtp_nms_scan": (i32, [p, i64, i64, p, p, p]),
     "mtp_max_iou_assign": (i32, [p, p, p, i64, i64, i32, f32, f32, f32, f32, i32, i32, p, p, p, p, i64, p]),
+    "mtp_rpn_anchors": (i32, [p, i64, i64, i64, i64, i64, i64, i64, i64, i64, f32, p, p, p]),
+    "mtp_rpn_loss_workspace_bytes": (i64, [i64, i64]),
+    "mtp_rpn_loss": (i32, [C.POINTER(RpnLevel), i32, i64, p, i64, p, i64, p, p, p, p, i64, i64, C.POINTER(f32), C.POINTER(f32), f32, f32, f32, p, p, p, i64, p]),
+    "mtp_rpn_proposals": (i32, [C.POINTER(RpnLevel), i32, i64, p, i64, p, i64, C.POINTER(f32), C.POINTER(f32), f32, p, p, p, p, p, p]),
+    "mtp_rpn_encode": (i32, [p, p, C.POINTER(f32), C.POINTER(f32), i64, p, p]),
+    "mtp_rpn_decode": (i32, [p, p, C.POINTER(f32), C.POINTER(f32), i64, p, p]),
     "mtp_version": (C.c_char_p, []),
     "mtp_stream_create_low_priority": (i32, [p]),
     "mtp_stream_create_cu_mask": (i32, [p, i32, p]),

@@ -1455,3 +1455,150 @@ def max_iou_assign(gts, priors, gt_labels, calculator, pos_iou_thr, neg_iou_thr,
                                    int(bool(match_low_quality)), int(bool(gt_max_assign_all)), _p(gt_inds), _f32(max_overlaps), _p(labels), _p(ws), K * 8,
                                    _s()), "mtp_max_iou_assign")
     return gt_inds, max_overlaps, labels
+
+
+# ------------------------------------------------------------------------------------------------ oriented RPN (csrc/rpn.hip)
+RPN_MAX_LEVELS = _lib.RPN_MAX_LEVELS
+RPN_DELTAS = 6
+
+
+def rpn_map_nchw(t):
+    """a level's map in mmdet's layout (N, A * C, H, W), contiguous f32 -> (tensor, element offset, strides (image, channel, y, x))"""
+    N, Cc, H, W = t.shape
+    return t, 0, (Cc * H * W, H * W, W, 1)
+
+
+def rpn_map_rows(t, H, W, col0=0, row0=0):
+    """a level's map in the engines' row layout: rows row0 .. row0 + N * H * W of t (., ld), channel c at column col0 + c"""
+    ld = t.shape[1]
+    return t, row0 * ld + col0, (H * W * ld, 1, W * ld, ld)
+
+
+def _rpn_codec(means, stds):
+    m, s = [float(v) for v in means], [float(v) for v in stds]
+    if len(m) != RPN_DELTAS or len(s) != RPN_DELTAS or min(s) <= 0:
+        raise ValueError("the midpoint-offset coder takes 6 means and 6 positive stds")
+    return (C.c_float * 6)(*m), (C.c_float * 6)(*s)
+
+
+def _rpn_levels(cls_maps, reg_maps, sizes, A, images, dcls=None, dreg=None, keep_counts=None):
+    """-> (mtp_rpn_level array, number of anchors); every address a kernel can form from the strides lies inside its tensor"""
+    n = len(sizes)
+    if not 1 <= n <= RPN_MAX_LEVELS or len(cls_maps) != n or len(reg_maps) != n:
+        raise ValueError("rpn: 1 .. %d levels, one cls and one reg map each" % RPN_MAX_LEVELS)
+    arr = (_lib.RpnLevel * n)()
+    total = 0
+
+    def addr(m, channels, H, W, like=None):
+        t, off, st = m
+        if t.dtype != torch.float32:
+            raise TypeError("rpn: the maps are float32")
+        if like is not None and (like[1] != off or tuple(like[2]) != tuple(st) or like[0].numel() != t.numel()):
+            raise ValueError("rpn: a gradient map has the layout of its map")
+        last = off + (images - 1) * st[0] + (channels - 1) * st[1] + (H - 1) * st[2] + (W - 1) * st[3]
+        if off < 0 or min(st) < 0 or last >= t.numel():
+            raise ValueError("rpn: a map's strides reach past its tensor")
+        return _p(t) + 4 * off
+
+    for i, (H, W) in enumerate(sizes):
+        lv = arr[i]
+        lv.cls, lv.reg = addr(cls_maps[i], A, H, W), addr(reg_maps[i], A * RPN_DELTAS, H, W)
+        if dcls is not None:
+            lv.dcls, lv.dreg = addr(dcls[i], A, H, W, cls_maps[i]), addr(dreg[i], A * RPN_DELTAS, H, W, reg_maps[i])
+        lv.H, lv.W = H, W
+        lv.keep_count = 0 if keep_counts is None else int(keep_counts[i])
+        lv.cls_stride, lv.reg_stride = (C.c_int64 * 4)(*cls_maps[i][2]), (C.c_int64 * 4)(*reg_maps[i][2])
+        total += H * W * A
+    return arr, total
+
+
+def rpn_anchors(base_anchors, H, W, stride, pad_shape, img_shape, allowed_border=0, priors=None, flags=None):
+    """base_anchors (A, 4) f32 on the device -> priors (H W A, 4) f32, inside flags (H W A) uint8.  stride: (w, h)."""
+    _check_boxes("rpn_anchors", base_anchors, 4)
+    A = base_anchors.shape[0]
+    n = H * W * A
+    priors = _scratch((n, 4), base_anchors.device, torch.float32) if priors is None else priors
+    flags = _scratch((n,), base_anchors.device, torch.uint8) if flags is None else flags
+    assert tuple(priors.shape) == (n, 4) and flags.dtype == torch.uint8 and tuple(flags.shape) == (n,)
+    check(lib().mtp_rpn_anchors(_f32(base_anchors), A, H, W, int(stride[0]), int(stride[1]), int(pad_shape[0]), int(pad_shape[1]), int(img_shape[0]),
+                                int(img_shape[1]), float(allowed_border), _f32(priors), _p(flags), _s()), "mtp_rpn_anchors")
+    return priors, flags
+
+
+def rpn_loss(cls_maps, reg_maps, sizes, A, priors, gts, samples, sample_gt, n_pos, n_neg, means, stds, beta, cls_weight=1.0, bbox_weight=1.0,
+             dcls=None, dreg=None, loss_cls=None, loss_bbox=None):
+    """Targets and loss of the oriented RPN for the whole batch (mtp_rpn_loss): two launches, no host synchronisation.  cls_maps / reg_maps: per level
+    an rpn_map_nchw / rpn_map_rows triple; sizes: per level (H, W); priors (sum H W A, 4); gts (K, 5) of all images (K may be 0); samples, sample_gt
+    (images, S) int64; n_pos, n_neg (images) int64.  dcls / dreg: gradient maps in the maps' layout, ZEROED by the caller (both or neither).
+    -> (loss_cls (levels), loss_bbox (levels)) f32"""
+    _check_boxes("rpn_loss", priors, 4)
+    _check_boxes("rpn_loss", gts, 5)
+    images, S = samples.shape
+    if (dcls is None) != (dreg is None):
+        raise ValueError("rpn_loss: dcls and dreg come together")
+    arr, total = _rpn_levels(cls_maps, reg_maps, sizes, A, images, dcls, dreg)
+    if priors.shape[0] != total:
+        raise ValueError("rpn_loss: %d priors for %d anchors" % (priors.shape[0], total))
+    for t, shape in ((samples, (images, S)), (sample_gt, (images, S)), (n_pos, (images,)), (n_neg, (images,))):
+        if t.dtype != torch.int64 or tuple(t.shape) != shape:
+            raise TypeError("rpn_loss: samples, sample_gt (images, S) and n_pos, n_neg (images) are int64")
+    dev, n = priors.device, len(sizes)
+    loss_cls = _scratch((n,), dev, torch.float32) if loss_cls is None else loss_cls
+    loss_bbox = _scratch((n,), dev, torch.float32) if loss_bbox is None else loss_bbox
+    assert tuple(loss_cls.shape) == tuple(loss_bbox.shape) == (n,)
+    wb = lib().mtp_rpn_loss_workspace_bytes(images, S)
+    ws = _scratch((wb // 4,), dev, torch.float32)
+    m, s = _rpn_codec(means, stds)
+    K = gts.shape[0]
+    check(lib().mtp_rpn_loss(arr, n, A, _f32(priors), total, _f32(gts) if K else None, K, _p(samples), _p(sample_gt), _p(n_pos), _p(n_neg), images, S, m, s,
+                             float(beta), float(cls_weight), float(bbox_weight), _f32(loss_cls), _f32(loss_bbox), _p(ws), wb, _s()), "mtp_rpn_loss")
+    return loss_cls, loss_bbox
+
+
+def rpn_proposals(cls_maps, reg_maps, sizes, A, priors, keep, keep_counts, means, stds, min_bbox_size=0.0, out=None):
+    """keep (images, T) int64, T = sum(keep_counts): per level the kept anchors (indices into the level's own H W A), level after level.
+    -> scores (images, T) f32, rboxes (images, T, 5), hboxes (images, T, 4), level_ids (images, T) int64, valid (images, T) uint8.  One launch."""
+    _check_boxes("rpn_proposals", priors, 4)
+    images, T = keep.shape
+    if keep.dtype != torch.int64 or T != sum(int(k) for k in keep_counts) or T == 0:
+        raise TypeError("rpn_proposals: keep must be int64 of shape (images, sum(keep_counts) > 0)")
+    arr, total = _rpn_levels(cls_maps, reg_maps, sizes, A, images, keep_counts=keep_counts)
+    if priors.shape[0] != total:
+        raise ValueError("rpn_proposals: %d priors for %d anchors" % (priors.shape[0], total))
+    dev = priors.device
+    if out is None:
+        out = (_scratch((images, T), dev, torch.float32), _scratch((images, T, 5), dev, torch.float32), _scratch((images, T, 4), dev, torch.float32),
+               _scratch((images, T), dev, torch.int64), _scratch((images, T), dev, torch.uint8))
+    scores, rboxes, hboxes, level_ids, valid = out
+    assert tuple(scores.shape) == tuple(level_ids.shape) == tuple(valid.shape) == (images, T) and level_ids.dtype == torch.int64 and valid.dtype == torch.uint8
+    assert tuple(rboxes.shape) == (images, T, 5) and tuple(hboxes.shape) == (images, T, 4)
+    m, s = _rpn_codec(means, stds)
+    check(lib().mtp_rpn_proposals(arr, len(sizes), A, _f32(priors), total, _p(keep), images, m, s, float(min_bbox_size), _f32(scores), _f32(rboxes),
+                                  _f32(hboxes), _p(level_ids), _p(valid), _s()), "mtp_rpn_proposals")
+    return scores, rboxes, hboxes, level_ids, valid
+
+
+def rpn_encode(priors, gts, means, stds, out=None):
+    """midpoint-offset encode: priors (n, 4), gts (n, 5) -> deltas (n, 6)"""
+    _check_boxes("rpn_encode", priors, 4)
+    _check_boxes("rpn_encode", gts, 5)
+    n = priors.shape[0]
+    assert gts.shape[0] == n and n > 0
+    out = _scratch((n, 6), priors.device, torch.float32) if out is None else out
+    assert tuple(out.shape) == (n, 6)
+    m, s = _rpn_codec(means, stds)
+    check(lib().mtp_rpn_encode(_f32(priors), _f32(gts), m, s, n, _f32(out), _s()), "mtp_rpn_encode")
+    return out
+
+
+def rpn_decode(priors, deltas, means, stds, out=None):
+    """midpoint-offset decode: priors (n, 4), deltas (n, 6) -> rotated boxes (n, 5), w >= h, theta in [-pi/2, pi/2)"""
+    _check_boxes("rpn_decode", priors, 4)
+    _check_boxes("rpn_decode", deltas, 6)
+    n = priors.shape[0]
+    assert deltas.shape[0] == n and n > 0
+    out = _scratch((n, 5), priors.device, torch.float32) if out is None else out
+    assert tuple(out.shape) == (n, 5)
+    m, s = _rpn_codec(means, stds)
+    check(lib().mtp_rpn_decode(_f32(priors), _f32(deltas), m, s, n, _f32(out), _s()), "mtp_rpn_decode")
+    return out
