@@ -755,6 +755,57 @@ int mtp_rpn_proposals(const mtp_rpn_level* levels, int num_levels, int64_t A, co
 int mtp_rpn_encode(const float* priors, const float* gts, const float* means, const float* stds, int64_t n, float* deltas, mtp_stream_t stream);
 int mtp_rpn_decode(const float* priors, const float* deltas, const float* means, const float* stds, int64_t n, float* rboxes, mtp_stream_t stream);
 
+/* ---- the oriented RoI head (csrc/roi_head.hip): RoIAlignRotated (mmcv roi_align_rotated, aligned=True), DeltaXYWHTRBBoxCoder ('le90', edge_swap,
+ * proj_xy), targets + loss of the class-agnostic 2-FC bbox head, per-RoI prediction.  f32, int64 indices, no float atomics, two calls on the same
+ * inputs give the same bits (of these entry points: the head's layers run on mtp_gemm_tn, whose colsum by-product adds with atomics).  A level's map is addressed by element strides (image, channel, y, x).  rois (R, 6): image, cx, cy, w, h, theta in image
+ * coordinates.  The level of a RoI is floor(log2(sqrt(w h) / finest_scale + 1e-6)) clamped to the levels, or roi_levels[r] (int32) when given.
+ * valid (R / per_group) int64 on the device, or NULL: slot r is in use iff r % per_group < valid[r / per_group]; a slot that is not in use (or names
+ * no image) writes zeros and reads nothing. ---- */
+#define MTP_ROI_MAX_LEVELS 8
+typedef struct mtp_roi_level {
+    const float* map;      /* the feature map (forward) */
+    float* dmap;           /* its gradient in the same strides (backward gather) */
+    int64_t H, W;
+    float spatial_scale;   /* 1 / stride */
+    int64_t stride[4];
+} mtp_roi_level;
+/* out (R, out_size^2, C): bin-major, channel last; levels_out (R) int32 or NULL: the level used, -1 for a slot not in use.  One launch, one
+ * workgroup per RoI; out_size^2 * sample_num^2 <= 1024. */
+int mtp_roi_align_rotated_fwd(const mtp_roi_level* levels, int num_levels, int64_t images, int64_t C, const float* rois, const int32_t* roi_levels,
+                              const int64_t* valid, int64_t R, int64_t per_group, int out_size, int sample_num, int clockwise, float finest_scale,
+                              float* out, int32_t* levels_out, mtp_stream_t stream);
+/* the backward in two launches around a stable sort of the keys (the caller's): bwd_entries writes R * out_size^2 * sample_num^2 * 4 (key, weight)
+ * entries (mtp_roi_align_rotated_entries of them), key = the touched pixel in (level, image, y, x) order or the number of pixels where nothing is
+ * touched; bwd_gather takes the keys sorted ascending, order = the entry each sorted position came from, and dout (R, out_size^2, C): the first
+ * position of every run of equal keys owns the pixel, adds the run in sorted order and stores into dmap (accumulate: adds to what is there). */
+int64_t mtp_roi_align_rotated_entries(int64_t R, int out_size, int sample_num);
+int mtp_roi_align_rotated_bwd_entries(const mtp_roi_level* levels, int num_levels, int64_t images, const float* rois, const int32_t* roi_levels,
+                                      const int64_t* valid, int64_t R, int64_t per_group, int out_size, int sample_num, int clockwise,
+                                      float finest_scale, int64_t* keys, float* weights, mtp_stream_t stream);
+int mtp_roi_align_rotated_bwd_gather(const mtp_roi_level* levels, int num_levels, int64_t images, int64_t C, const float* dout,
+                                     const int64_t* sorted_keys, const int64_t* order, const float* weights, int64_t R, int out_size, int sample_num,
+                                     int accumulate, mtp_stream_t stream);
+/* the coder on plain arrays: priors (n, 5), gts (n, 5) -> deltas (n, 5); priors (n, 5), deltas (n, 5) -> rboxes (n, 5), w >= h, theta in
+ * [-pi/2, pi/2).  means, stds: 5 HOST floats each. */
+int mtp_rbox_delta_encode(const float* priors, const float* gts, const float* means, const float* stds, int64_t n, float* deltas, mtp_stream_t stream);
+int mtp_rbox_delta_decode(const float* priors, const float* deltas, const float* means, const float* stds, int64_t n, float* rboxes, mtp_stream_t stream);
+int64_t mtp_roi_loss_workspace_bytes(int64_t images, int64_t samples);
+/* Targets and both losses of the whole batch, forward and backward, two launches.  Row b * S + j is slot j of image b: n_pos[b] positives, then
+ * n_neg[b] negatives, then padding.  cls_score (images S, ld_cls): num_classes + 1 logits per row; bbox_pred (images S, ld_reg): 5 deltas; rois
+ * (images S, 5); gts (num_gts, 5) and gt_labels (num_gts) of all images; sample_gt (images, S): on positives the row of gts.  Label = the gt's on
+ * positives, num_classes on negatives.  losses[0] = cls_weight * sum CE / max(R_total, 1), losses[1] = bbox_weight * sum SmoothL1(beta) over the
+ * positives' five deltas / R_total, losses[2] = top-1 accuracy in percent over the R_total rows in use, R_total = sum (n_pos + n_neg) read on the
+ * device.  dcls / dreg (both or neither): the gradients of losses[0] + losses[1] in the layout of cls_score / bbox_pred, every row stored (zeros on
+ * padding).  workspace: mtp_roi_loss_workspace_bytes(images, S). */
+int mtp_roi_loss(const float* cls_score, int64_t ld_cls, const float* bbox_pred, int64_t ld_reg, int64_t num_classes, const float* rois,
+                 const float* gts, const int64_t* gt_labels, int64_t num_gts, const int64_t* sample_gt, const int64_t* n_pos, const int64_t* n_neg,
+                 int64_t images, int64_t S, const float* means, const float* stds, float beta, float cls_weight, float bbox_weight, float* losses,
+                 float* dcls, float* dreg, void* workspace, int64_t workspace_bytes, mtp_stream_t stream);
+/* per RoI: scores (R, num_classes) = softmax without the background column, boxes (R, 5) = decode(rois (R, 5), bbox_pred), flags (R, num_classes)
+ * bytes = score > score_thr.  One launch. */
+int mtp_roi_predict(const float* cls_score, int64_t ld_cls, const float* bbox_pred, int64_t ld_reg, int64_t num_classes, const float* rois, int64_t R,
+                    const float* means, const float* stds, float score_thr, float* scores, float* boxes, uint8_t* flags, mtp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

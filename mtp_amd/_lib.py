@@ -96,6 +96,14 @@ class RpnLevel(C.Structure):
     _fields_ = [("cls", p), ("reg", p), ("dcls", p), ("dreg", p), ("H", i64), ("W", i64), ("keep_count", i64), ("cls_stride", i64 * 4), ("reg_stride", i64 * 4)]
 
 
+ROI_MAX_LEVELS = 8
+
+
+class RoiLevel(C.Structure):
+    """struct mtp_roi_level"""
+    _fields_ = [("map", p), ("dmap", p), ("H", i64), ("W", i64), ("spatial_scale", f32), ("stride", i64 * 4)]
+
+
 # name -> (restype, argtypes); must list EVERY function declared in include/mtp_hip.h (tests/test_abi.py checks)
 SIGNATURES = {
     "mtp_weight_images": (i32, [p, i32, i64, i32, p]),
@@ -228,6 +236,15 @@ SIGNATURES = {
     "mtp_rpn_proposals": (i32, [C.POINTER(RpnLevel), i32, i64, p, i64, p, i64, C.POINTER(f32), C.POINTER(f32), f32, p, p, p, p, p, p]),
     "mtp_rpn_encode": (i32, [p, p, C.POINTER(f32), C.POINTER(f32), i64, p, p]),
     "mtp_rpn_decode": (i32, [p, p, C.POINTER(f32), C.POINTER(f32), i64, p, p]),
+    "mtp_roi_align_rotated_fwd": (i32, [C.POINTER(RoiLevel), i32, i64, i64, p, p, p, i64, i64, i32, i32, i32, f32, p, p, p]),
+    "mtp_roi_align_rotated_entries": (i64, [i64, i32, i32]),
+    "mtp_roi_align_rotated_bwd_entries": (i32, [C.POINTER(RoiLevel), i32, i64, p, p, p, i64, i64, i32, i32, i32, f32, p, p, p]),
+    "mtp_roi_align_rotated_bwd_gather": (i32, [C.POINTER(RoiLevel), i32, i64, i64, p, p, p, p, i64, i32, i32, i32, p]),
+    "mtp_rbox_delta_encode": (i32, [p, p, C.POINTER(f32), C.POINTER(f32), i64, p, p]),
+    "mtp_rbox_delta_decode": (i32, [p, p, C.POINTER(f32), C.POINTER(f32), i64, p, p]),
+    "mtp_roi_loss_workspace_bytes": (i64, [i64, i64]),
+    "mtp_roi_loss": (i32, [p, i64, p, i64, i64, p, p, p, i64, p, p, p, i64, i64, C.POINTER(f32), C.POINTER(f32), f32, f32, f32, p, p, p, p, i64, p]),
+    "mtp_roi_predict": (i32, [p, i64, p, i64, i64, p, i64, C.POINTER(f32), C.POINTER(f32), f32, p, p, p, p]),
     "mtp_version": (C.c_char_p, []),
     "mtp_stream_create_low_priority": (i32, [p]),
     "mtp_stream_create_cu_mask": (i32, [p, i32, p]),

@@ -1602,3 +1602,181 @@ def rpn_decode(priors, deltas, means, stds, out=None):
     m, s = _rpn_codec(means, stds)
     check(lib().mtp_rpn_decode(_f32(priors), _f32(deltas), m, s, n, _f32(out), _s()), "mtp_rpn_decode")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ oriented RoI head (csrc/roi_head.hip)
+ROI_MAX_LEVELS = _lib.ROI_MAX_LEVELS
+ROI_DELTAS = 5
+ROI_MAX_POINTS = 1024      # out_size^2 * sample_num^2: the sample points of one RoI live in LDS
+
+
+def _roi_codec(means, stds):
+    m, s = [float(v) for v in means], [float(v) for v in stds]
+    if len(m) != ROI_DELTAS or len(s) != ROI_DELTAS or min(s) <= 0:
+        raise ValueError("the delta-xywht coder takes 5 means and 5 positive stds")
+    return (C.c_float * 5)(*m), (C.c_float * 5)(*s)
+
+
+def _roi_levels(maps, sizes, scales, images, channels, grads=False):
+    """maps: per level an rpn_map_nchw / rpn_map_rows triple (the gradient maps when grads) -> mtp_roi_level array; every address a kernel can form
+    from the strides lies inside its tensor"""
+    n = len(sizes)
+    if not 1 <= n <= ROI_MAX_LEVELS or len(scales) != n or (maps is not None and len(maps) != n):
+        raise ValueError("roi_align_rotated: 1 .. %d levels, one map and one spatial scale each" % ROI_MAX_LEVELS)
+    arr = (_lib.RoiLevel * n)()
+    for i, (H, W) in enumerate(sizes):
+        lv = arr[i]
+        lv.H, lv.W, lv.spatial_scale = int(H), int(W), float(scales[i])
+        if maps is None:
+            continue
+        t, off, st = maps[i]
+        if t.dtype != torch.float32:
+            raise TypeError("roi_align_rotated: the maps are float32")
+        last = off + (images - 1) * st[0] + (channels - 1) * st[1] + (H - 1) * st[2] + (W - 1) * st[3]
+        if off < 0 or min(st) < 0 or last >= t.numel():
+            raise ValueError("roi_align_rotated: a map's strides reach past its tensor")
+        if grads:
+            lv.dmap = _p(t) + 4 * off
+        else:
+            lv.map = _p(t) + 4 * off
+        lv.stride = (C.c_int64 * 4)(*st)
+    return arr
+
+
+def _roi_check(name, rois, roi_levels, valid, out_size, sample_num):
+    if rois.dtype != torch.float32 or rois.dim() != 2 or rois.shape[1] != 6 or rois.shape[0] == 0:
+        raise TypeError("%s: rois must be float32 of shape (R > 0, 6): image, cx, cy, w, h, theta" % name)
+    R = rois.shape[0]
+    if out_size < 1 or sample_num < 1 or out_size * out_size * sample_num * sample_num > ROI_MAX_POINTS:
+        raise ValueError("%s: out_size^2 * sample_num^2 must lie in 1 .. %d" % (name, ROI_MAX_POINTS))
+    if roi_levels is not None and (roi_levels.dtype != torch.int32 or tuple(roi_levels.shape) != (R,)):
+        raise TypeError("%s: roi_levels must be int32 of shape (R,)" % name)
+    per = 0
+    if valid is not None:
+        if valid.dtype != torch.int64 or valid.dim() != 1 or valid.numel() == 0 or R % valid.numel():
+            raise TypeError("%s: valid must be int64 (groups,) with R a multiple of groups" % name)
+        per = R // valid.numel()
+    return R, per
+
+
+def roi_align_rotated_fwd(maps, sizes, scales, channels, images, rois, out_size=7, sample_num=2, clockwise=False, finest_scale=56.0, roi_levels=None,
+                          valid=None, out=None, levels_out=None):
+    """RoIAlignRotated (aligned) of all RoIs over all levels in one launch.  maps: per level an rpn_map_nchw / rpn_map_rows triple; sizes (H, W) and
+    scales (1 / stride) per level; rois (R, 6) f32; roi_levels (R) int32 overrides the level map; valid (groups) int64: slot r is in use iff
+    r % (R / groups) < valid[r // (R / groups)].  -> out (R, out_size^2, channels) f32, bin-major and channel-last"""
+    R, per = _roi_check("roi_align_rotated_fwd", rois, roi_levels, valid, out_size, sample_num)
+    arr = _roi_levels(maps, sizes, scales, images, channels)
+    shape = (R, out_size * out_size, channels)
+    out = _scratch(shape, rois.device, torch.float32) if out is None else out
+    assert tuple(out.shape) == shape and (levels_out is None or (levels_out.dtype == torch.int32 and tuple(levels_out.shape) == (R,)))
+    check(lib().mtp_roi_align_rotated_fwd(arr, len(sizes), images, channels, _f32(rois), _p(roi_levels), _p(valid), R, per, out_size, sample_num,
+                                          int(bool(clockwise)), float(finest_scale), _f32(out), _p(levels_out), _s()), "mtp_roi_align_rotated_fwd")
+    return out
+
+
+def roi_align_rotated_bwd(dout, dmaps, sizes, scales, channels, images, rois, out_size=7, sample_num=2, clockwise=False, finest_scale=56.0,
+                          roi_levels=None, valid=None, accumulate=False):
+    """the gradient of roi_align_rotated_fwd with respect to the maps, deterministic: entries, a stable sort of their pixel keys, one owner per
+    touched pixel.  dout (R, out_size^2, channels); dmaps: per level a triple in the maps' layout.  Only the touched pixels are written: stored, or
+    added to what is there when accumulate -- the caller zeroes the maps otherwise.  No gradient to the RoIs (mmcv has none)."""
+    R, per = _roi_check("roi_align_rotated_bwd", rois, roi_levels, valid, out_size, sample_num)
+    if dout.dtype != torch.float32 or tuple(dout.shape) != (R, out_size * out_size, channels):
+        raise TypeError("roi_align_rotated_bwd: dout must be float32 of shape (R, out_size^2, channels)")
+    n = lib().mtp_roi_align_rotated_entries(R, out_size, sample_num)
+    keys, weights = _scratch((n,), rois.device, torch.int64), _scratch((n,), rois.device, torch.float32)
+    geo = _roi_levels(None, sizes, scales, images, channels)
+    check(lib().mtp_roi_align_rotated_bwd_entries(geo, len(sizes), images, _f32(rois), _p(roi_levels), _p(valid), R, per, out_size, sample_num,
+                                                  int(bool(clockwise)), float(finest_scale), _p(keys), _f32(weights), _s()),
+          "mtp_roi_align_rotated_bwd_entries")
+    skeys, order = torch.sort(keys, stable=True)
+    arr = _roi_levels(dmaps, sizes, scales, images, channels, grads=True)
+    check(lib().mtp_roi_align_rotated_bwd_gather(arr, len(sizes), images, channels, _f32(dout), _p(skeys.contiguous()), _p(order.contiguous()), _f32(weights),
+                                                 R, out_size, sample_num, int(bool(accumulate)), _s()), "mtp_roi_align_rotated_bwd_gather")
+    return dmaps
+
+
+def rbox_delta_encode(priors, gts, means, stds, out=None):
+    """DeltaXYWHTRBBoxCoder ('le90', edge_swap, proj_xy) encode: priors (n, 5), gts (n, 5) -> deltas (n, 5)"""
+    _check_boxes("rbox_delta_encode", priors, 5)
+    _check_boxes("rbox_delta_encode", gts, 5)
+    n = priors.shape[0]
+    assert gts.shape[0] == n and n > 0
+    out = _scratch((n, 5), priors.device, torch.float32) if out is None else out
+    assert tuple(out.shape) == (n, 5)
+    m, s = _roi_codec(means, stds)
+    check(lib().mtp_rbox_delta_encode(_f32(priors), _f32(gts), m, s, n, _f32(out), _s()), "mtp_rbox_delta_encode")
+    return out
+
+
+def rbox_delta_decode(priors, deltas, means, stds, out=None):
+    """decode: priors (n, 5), deltas (n, 5) -> rotated boxes (n, 5), w >= h, theta in [-pi/2, pi/2)"""
+    _check_boxes("rbox_delta_decode", priors, 5)
+    _check_boxes("rbox_delta_decode", deltas, 5)
+    n = priors.shape[0]
+    assert deltas.shape[0] == n and n > 0
+    out = _scratch((n, 5), priors.device, torch.float32) if out is None else out
+    assert tuple(out.shape) == (n, 5)
+    m, s = _roi_codec(means, stds)
+    check(lib().mtp_rbox_delta_decode(_f32(priors), _f32(deltas), m, s, n, _f32(out), _s()), "mtp_rbox_delta_decode")
+    return out
+
+
+def _roi_rows(name, t, cols):
+    """a (rows, >= cols) f32 view whose rows are ld apart -> (address, ld)"""
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < cols or t.stride(1) != 1 or not t.is_cuda:
+        raise TypeError("%s: expected float32 device rows of at least %d columns" % (name, cols))
+    return t.data_ptr(), t.stride(0)
+
+
+def roi_loss(cls_score, bbox_pred, num_classes, rois, gts, gt_labels, sample_gt, n_pos, n_neg, means, stds, beta=1.0, cls_weight=1.0, bbox_weight=1.0,
+             dcls=None, dreg=None, losses=None):
+    """Targets and losses of the RoI head for the whole batch (mtp_roi_loss): two launches, no host synchronisation.  cls_score (images * S,
+    num_classes + 1) and bbox_pred (images * S, 5): rows of a wider buffer are fine (column slices); rois (images * S, 5); gts (G, 5), gt_labels (G)
+    of all images; sample_gt (images, S), n_pos, n_neg (images) int64.  dcls / dreg: the gradients, in the layout of their inputs.
+    -> losses (3) f32: loss_cls, loss_bbox, acc in percent"""
+    images, S = sample_gt.shape
+    R = images * S
+    _check_boxes("roi_loss", rois, 5)
+    _check_boxes("roi_loss", gts, 5)
+    if rois.shape[0] != R or cls_score.shape[0] != R or bbox_pred.shape[0] != R:
+        raise ValueError("roi_loss: %d rows for %d x %d slots" % (rois.shape[0], images, S))
+    G = gts.shape[0]
+    for t, shape in ((sample_gt, (images, S)), (n_pos, (images,)), (n_neg, (images,)), (gt_labels, (G,))):
+        if t.dtype != torch.int64 or tuple(t.shape) != shape:
+            raise TypeError("roi_loss: sample_gt (images, S), n_pos, n_neg (images) and gt_labels (G) are int64")
+    (pc, ldc), (pr, ldr) = _roi_rows("roi_loss", cls_score, num_classes + 1), _roi_rows("roi_loss", bbox_pred, 5)
+    if (dcls is None) != (dreg is None):
+        raise ValueError("roi_loss: dcls and dreg come together")
+    pdc = pdr = None
+    if dcls is not None:
+        (pdc, a), (pdr, b) = _roi_rows("roi_loss", dcls, num_classes + 1), _roi_rows("roi_loss", dreg, 5)
+        if a != ldc or b != ldr or dcls.shape[0] != R or dreg.shape[0] != R:
+            raise ValueError("roi_loss: a gradient has the layout of its input")
+    dev = rois.device
+    losses = _scratch((3,), dev, torch.float32) if losses is None else losses
+    assert tuple(losses.shape) == (3,)
+    wb = lib().mtp_roi_loss_workspace_bytes(images, S)
+    ws = _scratch((wb // 4,), dev, torch.float32)
+    m, s = _roi_codec(means, stds)
+    check(lib().mtp_roi_loss(pc, ldc, pr, ldr, int(num_classes), _f32(rois), _f32(gts) if G else None, _p(gt_labels) if G else None, G, _p(sample_gt),
+                             _p(n_pos), _p(n_neg), images, S, m, s, float(beta), float(cls_weight), float(bbox_weight), _f32(losses), pdc, pdr, _p(ws), wb,
+                             _s()), "mtp_roi_loss")
+    return losses
+
+
+def roi_predict(cls_score, bbox_pred, num_classes, rois, means, stds, score_thr=0.0, out=None):
+    """per RoI the softmax scores (R, num_classes), the decoded box (R, 5) and the score > score_thr flags (R, num_classes) uint8: one launch"""
+    _check_boxes("roi_predict", rois, 5)
+    R = rois.shape[0]
+    if R == 0 or cls_score.shape[0] != R or bbox_pred.shape[0] != R:
+        raise ValueError("roi_predict: R > 0 rows of scores, deltas and rois")
+    (pc, ldc), (pr, ldr) = _roi_rows("roi_predict", cls_score, num_classes + 1), _roi_rows("roi_predict", bbox_pred, 5)
+    dev = rois.device
+    if out is None:
+        out = (_scratch((R, num_classes), dev, torch.float32), _scratch((R, 5), dev, torch.float32), _scratch((R, num_classes), dev, torch.uint8))
+    scores, boxes, flags = out
+    assert tuple(scores.shape) == tuple(flags.shape) == (R, num_classes) and tuple(boxes.shape) == (R, 5) and flags.dtype == torch.uint8
+    m, s = _roi_codec(means, stds)
+    check(lib().mtp_roi_predict(pc, ldc, pr, ldr, int(num_classes), _f32(rois), R, m, s, float(score_thr), _f32(scores), _f32(boxes), _p(flags), _s()),
+          "mtp_roi_predict")
+    return scores, boxes, flags
