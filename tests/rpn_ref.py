@@ -104,13 +104,16 @@ def level_of(idx, sizes, A):
     return lvl, cell // W, cell % W, a
 
 
-def loss(cls_maps, reg_maps, sizes, A, priors, gts_list, pos_list, pos_gt_list, neg_list, means, stds, beta, cls_weight=1.0, bbox_weight=1.0, dtype=F64):
+def loss(cls_maps, reg_maps, sizes, A, priors, gts_list, pos_list, pos_gt_list, neg_list, means, stds, beta, cls_weight=1.0, bbox_weight=1.0, dtype=F64,
+         avg_factor=None):
     """cls_maps[l] (N, A, H, W), reg_maps[l] (N, 6 A, H, W); per image the gts (K, 5), the positive anchors with their gt rows and the negative anchors
-    -> loss_cls (L), loss_bbox (L), dcls[l], dreg[l] (the gradients of the sum of all losses)"""
+    -> loss_cls (L), loss_bbox (L), dcls[l], dreg[l] (the gradients of the sum of all losses).  A gt row of -1 names no gt: the anchor is a positive
+    for the classification and has no box term.  avg_factor: the divisor, when it is not the number of listed anchors (the kernel counts the slots
+    of its lists, those whose anchor index it skips included)."""
     L = len(sizes)
     cls_maps, reg_maps = [np.asarray(m, dtype) for m in cls_maps], [np.asarray(m, dtype) for m in reg_maps]
     priors = np.asarray(priors, dtype)
-    avg = sum(len(p) + len(n) for p, n in zip(pos_list, neg_list))
+    avg = sum(len(p) + len(n) for p, n in zip(pos_list, neg_list)) if avg_factor is None else int(avg_factor)
     lc, lb = [np.zeros((), dtype) for _ in range(L)], [np.zeros((), dtype) for _ in range(L)]
     dcls, dreg = [np.zeros_like(m) for m in cls_maps], [np.zeros_like(m) for m in reg_maps]
     beta = dtype(beta)
@@ -126,7 +129,7 @@ def loss(cls_maps, reg_maps, sizes, A, priors, gts_list, pos_list, pos_gt_list, 
             z = cls_maps[l][b, a[j], y[j], x[j]]
             lc[l] = lc[l] + ((np.maximum(z, dtype(0)) - z * t[j]) + np.log1p(np.exp(-np.abs(z))))
             dcls[l][b, a[j], y[j], x[j]] = (dtype(1) / (dtype(1) + np.exp(-z)) - t[j]) * gc
-            if j < len(pos):
+            if j < len(pos) and pgt[j] >= 0:
                 ch = a[j] * 6 + np.arange(6)
                 d = reg_maps[l][b, ch, y[j], x[j]] - tgt[j]
                 ad = np.abs(d)
