@@ -715,6 +715,37 @@ int mtp_max_iou_assign(const float* gts, const float* priors, const int64_t* gt_
                        float neg_iou_lo, float neg_iou_hi, float min_pos_iou, int match_low_quality, int gt_max_assign_all, int64_t* gt_inds,
                        float* max_overlaps, int64_t* labels, void* workspace, int64_t workspace_bytes, mtp_stream_t stream);
 
+/* ---- the DOTA mAP metric of rotated detection (csrc/det_eval.hip; the reference's MTP_RD_Metric: tpfp_default, eval_rbbox_map, average_precision).
+ * Three launches whatever the number of images and classes; f32 boxes, int64 indices, integer atomics only, two calls give the same bits.
+ * Detection table: boxes (D, 5), scores (D), labels (D), img (D).  Gt table: boxes (G, 5), labels (G), ignore (G) u8, stored image by image, inside
+ * an image the non-ignored gts first, then the ignored ones, each in annotation order; gt_start (I + 1) the image offsets.  An image without a
+ * non-ignored gt counts as having no gts at all (its ignored ones included), as in the reference.  D in [1, 2^32 - 2], G >= 0 (gt pointers may be
+ * NULL when G == 0), T in [1, MTP_DET_MAX_THRS] thresholds read from HOST memory, K in [1, MTP_DET_MAX_CLASSES]. ---- */
+#define MTP_DET_MAX_THRS 8
+#define MTP_DET_MAX_CLASSES 4096
+#define MTP_DET_AP_POINTS 11
+typedef enum { MTP_DET_AP_11POINTS = 0, MTP_DET_AP_AREA = 1 } mtp_det_ap_mode;
+/* best_iou (D) f32 / best_gt (D): the largest IoU of detection d with the gts of its image and label and the FIRST gt (index into the gt table)
+ * attaining it; 0 / -1 where there is none.  winner (T, G) 64-bit words, ZEROED BY THE CALLER (winner_bytes >= T * G * 8, 8-byte aligned): for each
+ * threshold t with best_iou >= iou_thrs[t] (float32 compare) and a non-ignored gt, the maximum over the detections of
+ * (order-preserving u32 of the score) << 32 | (2^32 - 1 - d): the highest score, the lower index among equal scores. */
+int mtp_det_match(const float* det_boxes, const float* det_scores, const int64_t* det_labels, const int64_t* det_img, int64_t D,
+                  const float* gt_boxes, const int64_t* gt_labels, const uint8_t* gt_ignore, const int64_t* gt_start, int64_t I, int64_t G,
+                  const float* iou_thrs, int T, float* best_iou, int64_t* best_gt, void* winner, int64_t winner_bytes, mtp_stream_t stream);
+/* flags (T, D) u8: 1 = true positive (d owns winner[t][best_gt]), 2 = false positive (no gt, best_iou < iou_thrs[t], or a non-ignored gt owned by
+ * another detection), 0 = neither (the matched gt is ignored).  num_gts (K), ZEROED BY THE CALLER: += the non-ignored gts of each label in [0, K). */
+int mtp_det_tpfp(const float* det_scores, const float* best_iou, const int64_t* best_gt, int64_t D, const int64_t* gt_labels,
+                 const uint8_t* gt_ignore, int64_t G, const float* iou_thrs, int T, const void* winner, int64_t K, uint8_t* flags, int64_t* num_gts,
+                 mtp_stream_t stream);
+/* order (D): the detections class by class, inside a class by descending score; cls_start (K + 1) the class offsets into it; num_gts (K) an INPUT
+ * (summed over the ranks by the caller).  Per (t, k): cumulative tp / fp (exact), recall = tp / max(num_gts, eps32) in float64, precision =
+ * tp / max(tp + fp, eps32) in float32.  ap (T, K) f32: MTP_DET_AP_11POINTS = mean over the 11 HOST doubles recall_points of the maximum precision at
+ * recall >= point (0 where none), bit-equal to mmdet's average_precision; MTP_DET_AP_AREA = the area under the precision envelope (float64 sum in a
+ * fixed order; recall_points unused).  num_dets (K), last_recall (T, K) f64 (0 for a class without detections); recall (T, D) f64 / precision (T, D)
+ * f32 by list position when non-NULL.  D >= 0 here. */
+int mtp_det_ap(const uint8_t* flags, const int64_t* order, const int64_t* cls_start, const int64_t* num_gts, int64_t D, int64_t K, int T, int mode,
+               const double* recall_points, float* ap, int64_t* num_dets, double* last_recall, double* recall, float* precision, mtp_stream_t stream);
+
 /* ---- the oriented RPN (csrc/rpn.hip): anchors, the midpoint-offset coder (mmrotate's MidpointOffsetCoder, 'le90'), targets + loss, proposals.
  * f32 boxes and logits, int64 indices; no float atomics, two calls on the same inputs give the same bits.  The maps of a level are addressed by
  * element strides (image, channel, y, x): cls channel a, reg channel a * 6 + j for anchor a of A.  The levels tile the flat multi-level anchor

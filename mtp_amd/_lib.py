@@ -35,6 +35,9 @@ DCNV3_BWD_WINDOW_R2, DCNV3_BWD_WINDOW_R3, DCNV3_BWD_3X3_OS1, DCNV3_BWD_3X3_OS2, 
 # enum mtp_box_kind / mtp_assign_calculator (csrc/box_ops.hip)
 BOX_ALIGNED, BOX_ROTATED = 0, 1
 ASSIGN_BOX, ASSIGN_RBOX2HBOX, ASSIGN_ROTATED = 0, 1, 2
+# csrc/det_eval.hip: MTP_DET_MAX_THRS / MTP_DET_MAX_CLASSES / MTP_DET_AP_POINTS and enum mtp_det_ap_mode
+DET_MAX_THRS, DET_MAX_CLASSES, DET_AP_POINTS = 8, 4096, 11
+DET_AP_11POINTS, DET_AP_AREA = 0, 1
 
 # enum mtp_fuse_policy (mtp_fuse_pair_fwd / _bwd)
 FUSE_CONCAT, FUSE_SUM, FUSE_DIFF, FUSE_ABS_DIFF = 0, 1, 2, 3
@@ -230,6 +233,9 @@ SIGNATURES = {
     "mtp_nms_mask": (i32, [p, p, i64, i32, f32, p, i64, p]),
     "mtp_nms_scan": (i32, [p, i64, i64, p, p, p]),
     "mtp_max_iou_assign": (i32, [p, p, p, i64, i64, i32, f32, f32, f32, f32, i32, i32, p, p, p, p, i64, p]),
+    "mtp_det_match": (i32, [p, p, p, p, i64, p, p, p, p, i64, i64, C.POINTER(f32), i32, p, p, p, i64, p]),
+    "mtp_det_tpfp": (i32, [p, p, p, i64, p, p, i64, C.POINTER(f32), i32, p, i64, p, p, p]),
+    "mtp_det_ap": (i32, [p, p, p, p, i64, i64, i32, i32, C.POINTER(C.c_double), p, p, p, p, p, p]),
     "mtp_rpn_anchors": (i32, [p, i64, i64, i64, i64, i64, i64, i64, i64, i64, f32, p, p, p]),
     "mtp_rpn_loss_workspace_bytes": (i64, [i64, i64]),
     "mtp_rpn_loss": (i32, [C.POINTER(RpnLevel), i32, i64, p, i64, p, i64, p, p, p, p, i64, i64, C.POINTER(f32), C.POINTER(f32), f32, f32, f32, p, p, p, i64, p]),

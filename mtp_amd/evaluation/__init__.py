@@ -1,2 +1,3 @@
 from .iou_metric import IoUMetric  # noqa: F401
 from .accuracy import Accuracy  # noqa: F401
+from .dota_metric import DOTAMetric, eval_rbbox_map, rbox2qbox  # noqa: F401

@@ -1457,6 +1457,128 @@ def max_iou_assign(gts, priors, gt_labels, calculator, pos_iou_thr, neg_iou_thr,
     return gt_inds, max_overlaps, labels
 
 
+# ------------------------------------------------------------------------------------------------ DOTA mAP metric (csrc/det_eval.hip)
+DET_MAX_THRS, DET_MAX_CLASSES = _lib.DET_MAX_THRS, _lib.DET_MAX_CLASSES
+DET_MAX_DETS = (1 << 32) - 2      # the ownership key keeps 2^32 - 1 - index in 32 bits and is never 0
+DET_AP_MODE = {"11points": _lib.DET_AP_11POINTS, "area": _lib.DET_AP_AREA}
+# np.arange(0, 1 + 1e-3, 0.1) as mmdet's average_precision evaluates it: 0.30000000000000004, 0.6000000000000001, 0.7000000000000001, ... -- a
+# recall of exactly 3 / 10 does not reach the fourth point
+DET_AP_POINTS = tuple(float(i) * 0.1 for i in range(_lib.DET_AP_POINTS))
+
+
+def _det_thrs(name, iou_thrs):
+    thrs = [float(t) for t in iou_thrs]
+    if not 1 <= len(thrs) <= DET_MAX_THRS:
+        raise ValueError("%s: 1 to %d IoU thresholds, got %d" % (name, DET_MAX_THRS, len(thrs)))
+    return (C.c_float * len(thrs))(*thrs), len(thrs)
+
+
+def _det_typed(name, what, t, dtype, shape):
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise TypeError("%s: %s must be %s of shape %s, got %s %s" % (name, what, str(dtype).replace("torch.", ""), tuple(shape), t.dtype, tuple(t.shape)))
+
+
+def _det_count(name, D):
+    if not 0 < D <= DET_MAX_DETS:
+        raise ValueError("%s: 1 to 2^32 - 2 detections, got %d" % (name, D))
+
+
+def _det_gts(name, gt_labels, gt_ignore, G):
+    _det_typed(name, "gt_labels", gt_labels, torch.int64, (G,))
+    _det_typed(name, "gt_ignore", gt_ignore, torch.uint8, (G,))
+
+
+def det_match(det_boxes, det_scores, det_labels, det_img, gt_boxes, gt_labels, gt_ignore, gt_start, iou_thrs, best_iou=None, best_gt=None, winner=None):
+    """detections (D, 5) f32 / scores (D) f32 / labels (D) / img (D) int64 against the gt table (G, 5) f32 / labels (G) int64 / ignore (G) uint8 stored
+    image by image (non-ignored first), gt_start (I + 1) int64.  -> best_iou (D) f32, best_gt (D) int64 (-1: no gt of the label in the image),
+    winner (T, G) int64 ownership keys (zeroed here).  One launch, no sync."""
+    name = "det_match"
+    _check_boxes(name, det_boxes, 5)
+    _check_boxes(name, gt_boxes, 5)
+    D, G, I = det_boxes.shape[0], gt_boxes.shape[0], gt_start.shape[0] - 1
+    _det_count(name, D)
+    thrs, T = _det_thrs(name, iou_thrs)
+    _det_typed(name, "det_scores", det_scores, torch.float32, (D,))
+    _det_typed(name, "det_labels", det_labels, torch.int64, (D,))
+    _det_typed(name, "det_img", det_img, torch.int64, (D,))
+    _det_gts(name, gt_labels, gt_ignore, G)
+    if gt_start.dtype != torch.int64 or gt_start.dim() != 1 or I < 0:
+        raise TypeError("det_match: gt_start must be int64 of shape (images + 1,)")
+    dev = det_boxes.device
+    best_iou = _scratch((D,), dev, torch.float32) if best_iou is None else best_iou
+    best_gt = _scratch((D,), dev, torch.int64) if best_gt is None else best_gt
+    winner = _scratch((T, G), dev, torch.int64).zero_() if winner is None else winner
+    _det_typed(name, "best_iou", best_iou, torch.float32, (D,))
+    _det_typed(name, "best_gt", best_gt, torch.int64, (D,))
+    _det_typed(name, "winner", winner, torch.int64, (T, G))
+    g = (lambda t: _p(t)) if G else (lambda t: None)
+    check(lib().mtp_det_match(_f32(det_boxes), _f32(det_scores), _p(det_labels), _p(det_img), D, g(gt_boxes), g(gt_labels), g(gt_ignore), _p(gt_start), I,
+                              G, thrs, T, _f32(best_iou), _p(best_gt), g(winner), T * G * 8, _s()), "mtp_det_match")
+    return best_iou, best_gt, winner
+
+
+def det_tpfp(det_scores, best_iou, best_gt, gt_labels, gt_ignore, iou_thrs, winner, num_classes, flags=None, num_gts=None):
+    """-> flags (T, D) uint8 (1 true positive, 2 false positive, 0 matched to an ignored gt), num_gts (K) int64 = the non-ignored gts per label (zeroed
+    here).  One launch, no sync."""
+    name = "det_tpfp"
+    D, G, K = det_scores.shape[0], gt_labels.shape[0], int(num_classes)
+    _det_count(name, D)
+    thrs, T = _det_thrs(name, iou_thrs)
+    if not 0 < K <= DET_MAX_CLASSES:
+        raise ValueError("%s: 1 to %d classes, got %d" % (name, DET_MAX_CLASSES, K))
+    _det_typed(name, "det_scores", det_scores, torch.float32, (D,))
+    _det_typed(name, "best_iou", best_iou, torch.float32, (D,))
+    _det_typed(name, "best_gt", best_gt, torch.int64, (D,))
+    _det_gts(name, gt_labels, gt_ignore, G)
+    _det_typed(name, "winner", winner, torch.int64, (T, G))
+    dev = det_scores.device
+    flags = _scratch((T, D), dev, torch.uint8) if flags is None else flags
+    num_gts = _scratch((K,), dev, torch.int64).zero_() if num_gts is None else num_gts
+    _det_typed(name, "flags", flags, torch.uint8, (T, D))
+    _det_typed(name, "num_gts", num_gts, torch.int64, (K,))
+    g = (lambda t: _p(t)) if G else (lambda t: None)
+    check(lib().mtp_det_tpfp(_f32(det_scores), _f32(best_iou), _p(best_gt), D, g(gt_labels), g(gt_ignore), G, thrs, T, g(winner), K, _p(flags), _p(num_gts),
+                             _s()), "mtp_det_tpfp")
+    return flags, num_gts
+
+
+def det_ap(flags, order, cls_start, num_gts, mode="11points", curves=False, out=None):
+    """flags (T, D) uint8 in table order; order (D) int64: the detections class by class, by descending score inside a class; cls_start (K + 1) int64;
+    num_gts (K) int64.  -> ap (T, K) f32, num_dets (K) int64, last_recall (T, K) f64, and with curves the recall (T, D) f64 / precision (T, D) f32 by
+    list position (else None, None).  One launch, no sync.  D may be 0."""
+    name = "det_ap"
+    if mode not in DET_AP_MODE:
+        raise ValueError("det_ap: mode must be '11points' or 'area', got %r" % (mode,))
+    if flags.dtype != torch.uint8 or flags.dim() != 2:
+        raise TypeError("det_ap: flags must be uint8 of shape (T, D), got %s %s" % (flags.dtype, tuple(flags.shape)))
+    T, D = flags.shape
+    if not 1 <= T <= DET_MAX_THRS:
+        raise ValueError("det_ap: 1 to %d IoU thresholds, got %d" % (DET_MAX_THRS, T))
+    K = num_gts.shape[0]
+    if not 0 < K <= DET_MAX_CLASSES or D > DET_MAX_DETS:
+        raise ValueError("det_ap: 1 to %d classes and at most 2^32 - 2 detections, got %d and %d" % (DET_MAX_CLASSES, K, D))
+    _det_typed(name, "order", order, torch.int64, (D,))
+    _det_typed(name, "cls_start", cls_start, torch.int64, (K + 1,))
+    _det_typed(name, "num_gts", num_gts, torch.int64, (K,))
+    dev = num_gts.device
+    if out is None:
+        out = (_scratch((T, K), dev, torch.float32), _scratch((K,), dev, torch.int64), _scratch((T, K), dev, torch.float64),
+               _scratch((T, D), dev, torch.float64) if curves else None, _scratch((T, D), dev, torch.float32) if curves else None)
+    ap, num_dets, last_recall, recall, precision = out
+    _det_typed(name, "ap", ap, torch.float32, (T, K))
+    _det_typed(name, "num_dets", num_dets, torch.int64, (K,))
+    _det_typed(name, "last_recall", last_recall, torch.float64, (T, K))
+    if recall is not None:
+        _det_typed(name, "recall", recall, torch.float64, (T, D))
+    if precision is not None:
+        _det_typed(name, "precision", precision, torch.float32, (T, D))
+    d = (lambda t: _p(t)) if D else (lambda t: None)
+    pts = (C.c_double * len(DET_AP_POINTS))(*DET_AP_POINTS)
+    check(lib().mtp_det_ap(d(flags), d(order), _p(cls_start), _p(num_gts), D, K, T, DET_AP_MODE[mode], pts, _f32(ap), _p(num_dets), _p(last_recall),
+                           None if recall is None else d(recall), None if precision is None else d(precision), _s()), "mtp_det_ap")
+    return ap, num_dets, last_recall, recall, precision
+
+
 # ------------------------------------------------------------------------------------------------ oriented RPN (csrc/rpn.hip)
 RPN_MAX_LEVELS = _lib.RPN_MAX_LEVELS
 RPN_DELTAS = 6
