@@ -245,6 +245,20 @@ __global__ __launch_bounds__(256) void small_linear_dw_batched_kernel(SlBatch t,
     small_linear_dw_body<true>(t.dy[pi], t.x[pi], nullptr, nullptr, R, N, K, t.seg[pi], (int)blockIdx.z - pi * t.zsplit);
 }
 
+// ---- what the entry points refuse before any launch: the kernels keep R, N, K, C, Hp, Wp and the window count in an int (element offsets are int64), a grid takes 65535 in y and z
+inline bool size_ok(int64_t v) { return v > 0 && v < INT32_MAX; }
+// B images of (Hp, Wp) tokens of C channels: the window count is a grid x dimension and an int in the kernels, the element count an int64
+inline bool windows_ok(int64_t B, int64_t Hp, int64_t Wp, int64_t C) {
+    if (!size_ok(B) || !size_ok(Hp) || !size_ok(Wp) || !size_ok(C)) return false;
+    const RvsaWindows win(Hp, Wp);
+    return B < INT32_MAX / ((int64_t)win.nh * win.nw) && B * Hp * Wp <= INT64_MAX / C;      // (windows < 2^31: tokens < 49 * 2^31)
+}
+inline bool small_linear_ok(int64_t R, int64_t N, int64_t K) { return size_ok(R) && size_ok(N) && size_ok(K) && (K % 4) == 0; }
+constexpr int64_t kGridYZ = 65535;
+// grid of the dw kernels: 8 outputs in y, 4 * SL_DW_ROWS rows (times `count` problems) in z
+inline int64_t sl_dw_zsplit(int64_t R) { return (R + 4 * SL_DW_ROWS - 1) / (4 * SL_DW_ROWS); }
+inline bool sl_dw_grid_ok(int64_t R, int64_t N, int64_t count) { return (N + 7) / 8 <= kGridYZ && sl_dw_zsplit(R) * count <= kGridYZ; }
+
 }  // namespace
 
 // ---- the sampling heads of one RVSA block in ONE launch each way (VIT:344-358: zero pad, AvgPool2d(7, 7), LeakyReLU, three 1x1
@@ -327,7 +341,7 @@ __global__ __launch_bounds__(256) void rvsa_sampling_bwd_win_kernel(const float*
 }
 
 extern "C" int mtp_rvsa_sampling_bwd_win(const float* dsamp, const float* w, const float* avg, float* g, int64_t windows, int64_t C, int64_t N, mtp_stream_t stream) {
-    if (!dsamp || !w || !avg || !g || windows <= 0 || C <= 0 || (C % 4) || N <= 0 || N > 4096) return MTP_ERR_ARG;
+    if (!dsamp || !w || !avg || !g || !size_ok(windows) || !size_ok(C) || (C % 4) || N <= 0 || N > 4096) return MTP_ERR_ARG;
     const dim3 grid((unsigned)windows, (unsigned)((C / 4 + 63) / 64)), block(256);
     rvsa_sampling_bwd_win_kernel<<<grid, block, sizeof(float) * (size_t)N, (hipStream_t)stream>>>(dsamp, w, avg, g, (int)C, (int)N);
     return mtp_launch_status();
@@ -335,7 +349,7 @@ extern "C" int mtp_rvsa_sampling_bwd_win(const float* dsamp, const float* w, con
 
 extern "C" int mtp_rvsa_sampling_fwd(const void* x, int dtype, const float* w, const float* bias, float* avg, float* pooled, float* samp,
                                      int64_t B, int64_t Hp, int64_t Wp, int64_t C, int64_t N, mtp_stream_t stream) {
-    if (!x || !w || !avg || !pooled || !samp || B <= 0 || Hp <= 0 || Wp <= 0 || C <= 0 || (C % 4) || C > 8192 || N <= 0) return MTP_ERR_ARG;
+    if (!x || !w || !avg || !pooled || !samp || !windows_ok(B, Hp, Wp, C) || (C % 4) || C > 8192 || !size_ok(N)) return MTP_ERR_ARG;
     const RvsaWindows win(Hp, Wp);
     // workgroups per window (each pools the window again -- L2 reads -- and makes its share of the N outputs): round 2 measured 24.1 / 18.1 / 19.3 us at 1 / 2 / 4;
     // round 6, with the weight loads of a pass in flight together: 16.8 / 16.3 / 21.1 / 26.2 us at 1 / 2 / 3 / 5 (17.5 before) -- the repeated pooling, not the
@@ -351,7 +365,7 @@ extern "C" int mtp_rvsa_sampling_fwd(const void* x, int dtype, const float* w, c
 /* dx (T, C) ACT += (dsamp (R, N) . w (N, C)) * leaky'(avg) / 49, broadcast over each window's tokens */
 extern "C" int mtp_rvsa_sampling_bwd(const float* dsamp, const float* w, const float* avg, void* dx, int dtype,
                                      int64_t B, int64_t Hp, int64_t Wp, int64_t C, int64_t N, mtp_stream_t stream) {
-    if (!dsamp || !w || !avg || !dx || B <= 0 || Hp <= 0 || Wp <= 0 || C <= 0 || (C % 4) || N <= 0 || N > 4096) return MTP_ERR_ARG;
+    if (!dsamp || !w || !avg || !dx || !windows_ok(B, Hp, Wp, C) || (C % 4) || N <= 0 || N > 4096) return MTP_ERR_ARG;
     const RvsaWindows win(Hp, Wp);
     const dim3 grid((unsigned)(B * win.nh * win.nw), (unsigned)((C / 4 + 63) / 64)), block(256);
     const size_t lds = sizeof(float) * (size_t)N;
@@ -362,7 +376,7 @@ extern "C" int mtp_rvsa_sampling_bwd(const float* dsamp, const float* w, const f
 }
 
 extern "C" int mtp_rvsa_pool_fwd(const void* x, int dtype, float* avg, float* pooled, int64_t B, int64_t Hp, int64_t Wp, int64_t C, mtp_stream_t stream) {
-    if (!x || !avg || !pooled || B <= 0 || (C % 4)) return MTP_ERR_ARG;
+    if (!x || !avg || !pooled || !windows_ok(B, Hp, Wp, C) || (C % 4)) return MTP_ERR_ARG;
     const RvsaWindows win(Hp, Wp);
     const dim3 grid((unsigned)(B * win.nh * win.nw), (unsigned)((C / 4 + 255) / 256));
     return for_act(dtype, [&](auto t) {
@@ -371,7 +385,7 @@ extern "C" int mtp_rvsa_pool_fwd(const void* x, int dtype, float* avg, float* po
     });
 }
 extern "C" int mtp_rvsa_pool_bwd(const float* dpooled, const float* avg, void* dx, int dtype, int accumulate, int64_t B, int64_t Hp, int64_t Wp, int64_t C, mtp_stream_t stream) {
-    if (!dpooled || !avg || !dx || B <= 0 || (C % 4)) return MTP_ERR_ARG;
+    if (!dpooled || !avg || !dx || !windows_ok(B, Hp, Wp, C) || (C % 4)) return MTP_ERR_ARG;
     const RvsaWindows win(Hp, Wp);
     return for_act(dtype, [&](auto t) {
         using T = decltype(t);
@@ -381,7 +395,7 @@ extern "C" int mtp_rvsa_pool_bwd(const float* dpooled, const float* avg, void* d
 }
 
 extern "C" int mtp_small_linear_fwd(const float* x, const float* w, const float* b, float* y, int64_t R, int64_t N, int64_t K, mtp_stream_t stream) {
-    if (!x || !w || !y || R <= 0 || N <= 0 || (K % 4)) return MTP_ERR_ARG;
+    if (!x || !w || !y || !small_linear_ok(R, N, K)) return MTP_ERR_ARG;      // (K = 0 would pass K % 4 and clamp the weight index to -1)
     if (K <= 1024)
         small_linear_fwd_kernel<4, 4><<<dim3((unsigned)((R + 3) / 4)), kThreads, 0, (hipStream_t)stream>>>(x, w, b, y, (int)R, (int)N, (int)K);
     else if (K <= 2048)
@@ -391,7 +405,8 @@ extern "C" int mtp_small_linear_fwd(const float* x, const float* w, const float*
     return mtp_launch_status();
 }
 extern "C" int mtp_small_linear_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db, int64_t R, int64_t N, int64_t K, mtp_stream_t stream) {
-    if (!x || !w || !dy || R <= 0 || N <= 0 || (K % 4)) return MTP_ERR_ARG;
+    if (!x || !w || !dy || !small_linear_ok(R, N, K)) return MTP_ERR_ARG;
+    if ((dx && (R + 3) / 4 > kGridYZ) || (dw && !sl_dw_grid_ok(R, N, 1))) return MTP_ERR_ARG;      // before the clearing passes: a refusal writes nothing
     hipStream_t s = (hipStream_t)stream;
     if (dx) small_linear_dx_kernel<<<dim3((unsigned)((K + 1023) / 1024), (unsigned)((R + 3) / 4)), kThreads, 0, s>>>(dy, w, dx, (int)R, (int)N, (int)K);
     if (dw) {
@@ -401,7 +416,7 @@ extern "C" int mtp_small_linear_bwd(const float* x, const float* w, const float*
             (void)hipMemsetAsync(dw, 0, sizeof(float) * (size_t)(N * K), s);
             if (db) (void)hipMemsetAsync(db, 0, sizeof(float) * (size_t)N, s);
         }
-        const dim3 grid((unsigned)((K + 255) / 256), (unsigned)((N + 7) / 8), (unsigned)((R + 4 * SL_DW_ROWS - 1) / (4 * SL_DW_ROWS)));
+        const dim3 grid((unsigned)((K + 255) / 256), (unsigned)((N + 7) / 8), (unsigned)sl_dw_zsplit(R));
         small_linear_dw_kernel<false><<<grid, kThreads, 0, s>>>(dy, x, dw, db, (int)R, (int)N, (int)K, SlSegs{});
     }
     return mtp_launch_status();
@@ -410,7 +425,7 @@ extern "C" int mtp_small_linear_bwd(const float* x, const float* w, const float*
  * dw[j] += dy[:, r0_j : r0_j + rows_j]^T x.  Host arrays; db[j] may be NULL. */
 extern "C" int mtp_small_linear_dw_segments(const float* x, const float* dy, int64_t R, int64_t N, int64_t K, int nseg, const int64_t* seg_rows,
                                             float* const* dw, float* const* db, mtp_stream_t stream) {
-    if (!x || !dy || !seg_rows || !dw || R <= 0 || N <= 0 || K <= 0 || (K % 4) || nseg < 1 || nseg > 4) return MTP_ERR_ARG;
+    if (!x || !dy || !seg_rows || !dw || !small_linear_ok(R, N, K) || !sl_dw_grid_ok(R, N, 1) || nseg < 1 || nseg > 4) return MTP_ERR_ARG;
     SlSegs seg{};
     int64_t r = 0;
     for (int j = 0; j < nseg; ++j) {
@@ -423,7 +438,7 @@ extern "C" int mtp_small_linear_dw_segments(const float* x, const float* dy, int
     if (r != N) return MTP_ERR_ARG;
     seg.row0[nseg] = (int)N;
     seg.nseg = nseg;
-    const dim3 grid((unsigned)((K + 255) / 256), (unsigned)((N + 7) / 8), (unsigned)((R + 4 * SL_DW_ROWS - 1) / (4 * SL_DW_ROWS)));
+    const dim3 grid((unsigned)((K + 255) / 256), (unsigned)((N + 7) / 8), (unsigned)sl_dw_zsplit(R));
     small_linear_dw_kernel<true><<<grid, kThreads, 0, (hipStream_t)stream>>>(dy, x, (float*)nullptr, (float*)nullptr, (int)R, (int)N, (int)K, seg);
     return mtp_launch_status();
 }
@@ -432,7 +447,7 @@ extern "C" int mtp_small_linear_dw_segments(const float* x, const float* dy, int
  * count * nseg device pointers (problem-major) */
 extern "C" int mtp_small_linear_dw_segments_batched(const float* const* xs, const float* const* dys, int count, int64_t R, int64_t N, int64_t K, int nseg,
                                                     const int64_t* seg_rows, float* const* dw, float* const* db, mtp_stream_t stream) {
-    if (!xs || !dys || !seg_rows || !dw || count <= 0 || count > SL_BATCH || R <= 0 || N <= 0 || K <= 0 || (K % 4) || nseg < 1 || nseg > 4) return MTP_ERR_ARG;
+    if (!xs || !dys || !seg_rows || !dw || count <= 0 || count > SL_BATCH || !small_linear_ok(R, N, K) || !sl_dw_grid_ok(R, N, count) || nseg < 1 || nseg > 4) return MTP_ERR_ARG;
     SlBatch t{};
     for (int i = 0; i < count; ++i) {
         if (!xs[i] || !dys[i]) return MTP_ERR_ARG;
@@ -450,7 +465,7 @@ extern "C" int mtp_small_linear_dw_segments_batched(const float* const* xs, cons
         t.seg[i].row0[nseg] = (int)N;
         t.seg[i].nseg = nseg;
     }
-    t.zsplit = (int)((R + 4 * SL_DW_ROWS - 1) / (4 * SL_DW_ROWS));
+    t.zsplit = (int)sl_dw_zsplit(R);
     small_linear_dw_batched_kernel<<<dim3((unsigned)((K + 255) / 256), (unsigned)((N + 7) / 8), (unsigned)(t.zsplit * count)), kThreads, 0, (hipStream_t)stream>>>(t, (int)R, (int)N, (int)K);
     return mtp_launch_status();
 }

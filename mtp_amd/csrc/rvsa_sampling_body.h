@@ -21,12 +21,14 @@ __device__ __forceinline__ void rvsa_pool_window(const T* __restrict__ x, float*
             if (RB < 7 && a == RB) __builtin_amdgcn_sched_barrier(0);
             const int y = i * 7 + a - pad_t;
             const bool yok = y >= 0 && y < Hp;
-            const int yc = yok ? y : 0;
+            // a pad position loads the nearest token row / column, which lies in this window (the padding on either side is less than one window), and
+            // masks it: clamped to row / column 0 instead, a non-finite token there turned 0 * Inf into NaN in windows that do not hold it
+            const int yc = y < 0 ? 0 : (y < Hp ? y : Hp - 1);
             float4 v[7];
 #pragma unroll
             for (int bb = 0; bb < 7; ++bb) {
                 const int xx = j * 7 + bb - pad_l;
-                const int xc = (xx >= 0 && xx < Wp) ? xx : 0;
+                const int xc = xx < 0 ? 0 : (xx < Wp ? xx : Wp - 1);
                 v[bb] = load4(x + (((int64_t)b * Hp + yc) * Wp + xc) * C + 4 * c4);
             }
 #pragma unroll
