@@ -551,7 +551,7 @@ extern "C" int mtp_layernorm_bwd(const void* dy, int dy_dtype, const void* x, in
                                  float* dgamma_part, float* dbeta_part, int64_t part_ld, int64_t rows, int64_t C, mtp_stream_t stream) {
     if (part_ld == 0) part_ld = C;
     if (part_ld < C || (part_ld % 4)) return MTP_ERR_ARG;
-    if (!dy || !x || !mean || !rstd || !gamma || !dx || !dgamma_part || !dbeta_part || rows <= 0 || rows > INT32_MAX || (C % 4) || C > 256 * MAXV) return MTP_ERR_ARG;
+    if (!dy || !x || !mean || !rstd || !gamma || !dx || !dgamma_part || !dbeta_part || rows <= 0 || rows > INT32_MAX || C <= 0 || (C % 4) || C > 256 * MAXV) return MTP_ERR_ARG;
     if (fuse_gelu && !beta) return MTP_ERR_ARG;
     if (dx_copy && copy_dtype != dy_dtype) return MTP_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
@@ -573,7 +573,7 @@ extern "C" int mtp_layernorm_bwd_win(const void* dy, int dy_dtype, const void* x
                                      const float* win_add, int64_t B, int64_t Hp, int64_t Wp, mtp_stream_t stream) {
     if (part_ld == 0) part_ld = C;
     if (part_ld < C || (part_ld % 4)) return MTP_ERR_ARG;
-    if (!dy || !x || !mean || !rstd || !gamma || !dx || !dgamma_part || !dbeta_part || rows <= 0 || rows > INT32_MAX || (C % 4) || C > 256 * MAXV) return MTP_ERR_ARG;
+    if (!dy || !x || !mean || !rstd || !gamma || !dx || !dgamma_part || !dbeta_part || rows <= 0 || rows > INT32_MAX || C <= 0 || (C % 4) || C > 256 * MAXV) return MTP_ERR_ARG;
     if (!win_add || B <= 0 || Hp <= 0 || Wp <= 0 || B * Hp * Wp != rows) return MTP_ERR_ARG;
     if (dx_copy && copy_dtype != dy_dtype) return MTP_ERR_ARG;
     const RvsaWindows win(Hp, Wp);
@@ -640,11 +640,12 @@ extern "C" int mtp_reduce_rows_t_batched_f32(const float* const* parts, float* c
         if (!parts[i] || !outs[i]) return MTP_ERR_ARG;
         t.part[i] = parts[i];
         t.out[i] = outs[i];
-        if (!accumulate) {
+    }
+    if (!accumulate)      // after every entry has been checked: a refused call writes nothing
+        for (int i = 0; i < n; ++i) {
             hipError_t e = hipMemsetAsync(outs[i], 0, sizeof(float) * (size_t)(R * C), s);
             if (e != hipSuccess) return (int)e;
         }
-    }
     const int64_t col_blocks = (R * C + 255) / 256;
     int64_t splits = 1024 / col_blocks;
     if (splits < 1) splits = 1;
