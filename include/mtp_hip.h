@@ -837,6 +837,40 @@ int mtp_roi_loss(const float* cls_score, int64_t ld_cls, const float* bbox_pred,
 int mtp_roi_predict(const float* cls_score, int64_t ld_cls, const float* bbox_pred, int64_t ld_reg, int64_t num_classes, const float* rois, int64_t R,
                     const float* means, const float* stds, float score_thr, float* scores, float* boxes, uint8_t* flags, mtp_stream_t stream);
 
+/* ---- the mask branch of Mask R-CNN (csrc/mask_head.hip): RoIAlign (mmcv roi_align, pool_mode 'avg'), mask targets + mask loss (mmdet mask_target /
+ * crop_and_resize / mask_cross_entropy), mask paste (_do_paste_mask + threshold).  f32, int64 indices, no float atomics, two calls on the same
+ * inputs give the same bits.  Levels, valid and roi_levels as above; rois (R, 5): image, x1, y1, x2, y2 in image coordinates.  The level of a RoI
+ * is mmdet's map_roi_levels, floor(log2(sqrt((x2 - x1)(y2 - y1)) / finest_scale + 1e-6)) clamped to the levels.  sampling_ratio 1 .. 64, or 0: the
+ * adaptive grid ceil(roi_h / out_size) x ceil(roi_w / out_size).  A sample further than 1 px outside its map adds 0, otherwise it is clamped; of a
+ * bin's grid only the stretch that can fall inside is walked, so the work is bounded by the maps whatever the box.  out_size <= 32. ---- */
+/* out (R, out_size^2, C): bin-major, channel last; levels_out (R) int32 or NULL: the level used, -1 for a slot not in use.  One launch. */
+int mtp_roi_align_fwd(const mtp_roi_level* levels, int num_levels, int64_t images, int64_t C, const float* rois, const int32_t* roi_levels,
+                      const int64_t* valid, int64_t R, int64_t per_group, int out_size, int sampling_ratio, int aligned, float finest_scale, float* out,
+                      int32_t* levels_out, mtp_stream_t stream);
+/* the gradient with respect to the maps, one launch and no workspace: one wave per map pixel and 256 channels walks the RoIs in index order, 64 at a time (the
+ * bilinear weights are separable per axis).  EVERY pixel of every level's dmap is stored (accumulate: added to what is there). */
+int mtp_roi_align_bwd(const mtp_roi_level* levels, int num_levels, int64_t images, int64_t C, const float* dout, const float* rois,
+                      const int32_t* roi_levels, const int64_t* valid, int64_t R, int64_t per_group, int out_size, int sampling_ratio, int aligned,
+                      float finest_scale, int accumulate, mtp_stream_t stream);
+/* Mask targets and the mask loss of the whole batch, forward and backward, two launches.  Row b * S + j is slot j of image b: the first n_pos[b]
+ * slots (read on the device, clamped to 0 .. S) are positives, the rest padding.  mask_preds (images S, channels, M, M) logits, channels >= num_classes (the GEMM output padded to 8 columns is taken as it is): the
+ * labels name the first num_classes of them; boxes (images S,
+ * 4) x1, y1, x2, y2; labels (images S) the class channel, or NULL: channel 0 (class-agnostic); sample_gt (images, S) the row of bitmaps (num_gts, H,
+ * W) uint8; img_hw (images, 2) int64 on the device or NULL: the (h, w) of each image inside the H x W bitmaps, the box is clipped to it.  A slot with
+ * a row or a label out of range is padding.  targets (images S, M, M) uint8 = RoIAlign(bitmap, box, M, scale 1, adaptive grid, aligned) >= 0.5;
+ * target_avg (same shape, f32) or NULL: the value before the threshold; slot_loss (images S): the slot's sum of binary cross-entropies;
+ * loss[0] = loss_weight * sum / (n_pos_total M M), 0 without a positive; dlogits (like mask_preds) or NULL: its gradient, every element stored.  n_pos_total counts
+ * the first n_pos[b] slots of every image, whatever their rows and labels. */
+int mtp_mask_loss(const float* mask_preds, int64_t num_classes, int64_t channels, int mask_size, const float* boxes, const int64_t* labels, const int64_t* sample_gt,
+                  const int64_t* n_pos, int64_t images, int64_t S, const uint8_t* bitmaps, int64_t num_gts, int64_t H, int64_t W, const int64_t* img_hw,
+                  float loss_weight, uint8_t* targets, float* target_avg, float* slot_loss, float* loss, float* dlogits, mtp_stream_t stream);
+/* out (N, img_h, img_w) bytes: per instance the class channel (labels, or NULL: channel 0) of mask_preds (N, num_classes, M, M), through a sigmoid
+ * when activate (an instance whose label names no channel: an empty mask, all zeros), sampled bilinearly with zero padding (grid_sample, align_corners = false) at every pixel centre mapped through boxes (N, 4); an
+ * infinite normalised coordinate is 0.  threshold >= 0: value >= threshold as 0 / 1; threshold < 0: value * 255 truncated.  values (N, img_h,
+ * img_w) f32 or NULL: the sampled value.  One launch. */
+int mtp_mask_paste(const float* mask_preds, int64_t num_classes, int mask_size, const int64_t* labels, const float* boxes, int64_t N, int64_t img_h,
+                   int64_t img_w, float threshold, int activate, uint8_t* out, float* values, mtp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,8 +58,8 @@ from .task_modules import (AnchorGenerator, AssignResult, BboxOverlaps2D, Midpoi
                            RandomSampler, RBbox2HBboxOverlaps2D, RBboxOverlaps2D)
 from .task_modules import DeltaXYWHTRBBoxCoder  # noqa: F401
 from .dense_heads import OrientedRPNHead  # noqa: F401
-from .ops_roi import RoIAlignRotated  # noqa: F401
-from .roi_extractors import RotatedSingleRoIExtractor  # noqa: F401
-from .roi_heads import Shared2FCBBoxHead, StandardRoIHead  # noqa: F401
+from .ops_roi import RoIAlign, RoIAlignRotated  # noqa: F401
+from .roi_extractors import RotatedSingleRoIExtractor, SingleRoIExtractor  # noqa: F401
+from .roi_heads import FCNMaskHead, MaskRoIHead, Shared2FCBBoxHead, StandardRoIHead  # noqa: F401
 
 __version__ = "0.6.2"      # = mtp_version() of libmtp_hip.so ("mtp_hip 0.6.2 (gfx950)"): the round of the build

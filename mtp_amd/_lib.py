@@ -251,6 +251,10 @@ SIGNATURES = {
     "mtp_roi_loss_workspace_bytes": (i64, [i64, i64]),
     "mtp_roi_loss": (i32, [p, i64, p, i64, i64, p, p, p, i64, p, p, p, i64, i64, C.POINTER(f32), C.POINTER(f32), f32, f32, f32, p, p, p, p, i64, p]),
     "mtp_roi_predict": (i32, [p, i64, p, i64, i64, p, i64, C.POINTER(f32), C.POINTER(f32), f32, p, p, p, p]),
+    "mtp_roi_align_fwd": (i32, [C.POINTER(RoiLevel), i32, i64, i64, p, p, p, i64, i64, i32, i32, i32, f32, p, p, p]),
+    "mtp_roi_align_bwd": (i32, [C.POINTER(RoiLevel), i32, i64, i64, p, p, p, p, i64, i64, i32, i32, i32, f32, i32, p]),
+    "mtp_mask_loss": (i32, [p, i64, i64, i32, p, p, p, p, i64, i64, p, i64, i64, i64, p, f32, p, p, p, p, p, p]),
+    "mtp_mask_paste": (i32, [p, i64, i32, p, p, i64, i64, i64, f32, i32, p, p, p]),
     "mtp_version": (C.c_char_p, []),
     "mtp_stream_create_low_priority": (i32, [p]),
     "mtp_stream_create_cu_mask": (i32, [p, i32, p]),

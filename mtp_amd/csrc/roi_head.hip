@@ -15,28 +15,16 @@
 // The maps are addressed by element strides (image, channel, y, x) as mtp_rpn_level does.  Contraction is off: tests/roi_ref.py restates the same
 // operations in the same order.
 #include "common.h"
+#include "roi_levels.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kL = MTP_ROI_MAX_LEVELS;
 constexpr int kMaxEntries = 4096;                    // out_size^2 x sample_num^2 x 4 corners per RoI, in LDS
 constexpr float kPi = 3.14159265358979323846f;
 constexpr float kMaxRatio = 4.135166556742356f;      // |log(16 / 1000)|
 
-struct Level {
-    const float* map;
-    float* dmap;
-    int64_t H, W, first;      // first: the level's first pixel in the key order (level, image, y, x)
-    int64_t st[4];
-    float scale;
-};
-struct Levels {
-    Level lv[kL];
-    int n;
-    int64_t pixels;           // of all levels and images: the key of an entry that touches nothing
-};
 struct Geom {
     int P, S, clockwise;      // out_size, sample_num
     float finest;
@@ -393,27 +381,6 @@ bool make_codec(const float* means, const float* stds, Codec& k) {
         k.stdv[i] = stds[i];
         if (!(stds[i] > 0.0f)) return false;
     }
-    return true;
-}
-
-// need: 0 the geometry alone, 1 the maps, 2 the gradient maps
-bool make_levels(const mtp_roi_level* levels, int n, int64_t images, int need, Levels& L) {
-    if (!levels || n < 1 || n > kL || images < 1 || images > (1 << 20)) return false;
-    int64_t first = 0;
-    for (int i = 0; i < n; ++i) {
-        const mtp_roi_level& s = levels[i];
-        if ((need == 1 && !s.map) || (need == 2 && !s.dmap) || s.H < 1 || s.W < 1 || s.H > (1 << 20) || s.W > (1 << 20) || !(s.spatial_scale > 0.0f)) return false;
-        Level& d = L.lv[i];
-        d.map = s.map; d.dmap = s.dmap; d.H = s.H; d.W = s.W; d.first = first; d.scale = s.spatial_scale;
-        for (int c = 0; c < 4; ++c) {
-            if (s.stride[c] < 0) return false;
-            d.st[c] = s.stride[c];
-        }
-        first += images * s.H * s.W;
-    }
-    for (int i = n; i < kL; ++i) L.lv[i] = L.lv[n - 1];
-    L.n = n;
-    L.pixels = first;
     return true;
 }
 

@@ -1902,3 +1902,118 @@ def roi_predict(cls_score, bbox_pred, num_classes, rois, means, stds, score_thr=
     check(lib().mtp_roi_predict(pc, ldc, pr, ldr, int(num_classes), _f32(rois), R, m, s, float(score_thr), _f32(scores), _f32(boxes), _p(flags), _s()),
           "mtp_roi_predict")
     return scores, boxes, flags
+
+
+# ------------------------------------------------------------------------------------------------ the mask branch (csrc/mask_head.hip)
+ROI_ALIGN_MAX_OUT = 32          # out_size of roi_align_fwd / _bwd
+ROI_ALIGN_MAX_SAMPLING = 64     # a fixed sampling_ratio; 0 is the adaptive grid
+
+
+def _roi_align_check(name, rois, roi_levels, valid, out_size, sampling_ratio):
+    if rois.dtype != torch.float32 or rois.dim() != 2 or rois.shape[1] != 5 or rois.shape[0] == 0:
+        raise TypeError("%s: rois must be float32 of shape (R > 0, 5): image, x1, y1, x2, y2" % name)
+    R = rois.shape[0]
+    if not 1 <= out_size <= ROI_ALIGN_MAX_OUT or not 0 <= sampling_ratio <= ROI_ALIGN_MAX_SAMPLING:
+        raise ValueError("%s: out_size in 1 .. %d, sampling_ratio in 0 .. %d" % (name, ROI_ALIGN_MAX_OUT, ROI_ALIGN_MAX_SAMPLING))
+    if roi_levels is not None and (roi_levels.dtype != torch.int32 or tuple(roi_levels.shape) != (R,)):
+        raise TypeError("%s: roi_levels must be int32 of shape (R,)" % name)
+    per = 0
+    if valid is not None:
+        if valid.dtype != torch.int64 or valid.dim() != 1 or valid.numel() == 0 or R % valid.numel():
+            raise TypeError("%s: valid must be int64 (groups,) with R a multiple of groups" % name)
+        per = R // valid.numel()
+    return R, per
+
+
+def roi_align_fwd(maps, sizes, scales, channels, images, rois, out_size=14, sampling_ratio=0, aligned=True, finest_scale=56.0, roi_levels=None,
+                  valid=None, out=None, levels_out=None):
+    """RoIAlign (mmcv roi_align, 'avg') of all RoIs over all levels in one launch.  maps: per level an rpn_map_nchw / rpn_map_rows triple; sizes
+    (H, W) and scales (1 / stride) per level; rois (R, 5) f32: image, x1, y1, x2, y2; sampling_ratio 0: the adaptive grid; roi_levels (R) int32
+    overrides mmdet's level map; valid (groups) int64: slot r is in use iff r % (R / groups) < valid[r // (R / groups)].
+    -> out (R, out_size^2, channels) f32, bin-major and channel-last"""
+    R, per = _roi_align_check("roi_align_fwd", rois, roi_levels, valid, out_size, sampling_ratio)
+    arr = _roi_levels(maps, sizes, scales, images, channels)
+    shape = (R, out_size * out_size, channels)
+    out = _scratch(shape, rois.device, torch.float32) if out is None else out
+    assert tuple(out.shape) == shape and (levels_out is None or (levels_out.dtype == torch.int32 and tuple(levels_out.shape) == (R,)))
+    check(lib().mtp_roi_align_fwd(arr, len(sizes), images, channels, _f32(rois), _p(roi_levels), _p(valid), R, per, out_size, sampling_ratio,
+                                  int(bool(aligned)), float(finest_scale), _f32(out), _p(levels_out), _s()), "mtp_roi_align_fwd")
+    return out
+
+
+def roi_align_bwd(dout, dmaps, sizes, scales, channels, images, rois, out_size=14, sampling_ratio=0, aligned=True, finest_scale=56.0, roi_levels=None,
+                  valid=None, accumulate=False):
+    """the gradient of roi_align_fwd with respect to the maps, deterministic, one launch, no workspace: a gather per map pixel over the RoIs in
+    index order.  dout (R, out_size^2, channels); dmaps: per level a triple in the maps' layout.  EVERY pixel is stored, or added to what is
+    there when accumulate.  No gradient to the RoIs (mmcv has none)."""
+    R, per = _roi_align_check("roi_align_bwd", rois, roi_levels, valid, out_size, sampling_ratio)
+    if dout.dtype != torch.float32 or tuple(dout.shape) != (R, out_size * out_size, channels) or not dout.is_contiguous():
+        raise TypeError("roi_align_bwd: dout must be contiguous float32 of shape (R, out_size^2, channels)")
+    arr = _roi_levels(dmaps, sizes, scales, images, channels, grads=True)
+    check(lib().mtp_roi_align_bwd(arr, len(sizes), images, channels, _f32(dout), _f32(rois), _p(roi_levels), _p(valid), R, per, out_size,
+                                  sampling_ratio, int(bool(aligned)), float(finest_scale), int(bool(accumulate)), _s()), "mtp_roi_align_bwd")
+    return dmaps
+
+
+def mask_loss(mask_preds, boxes, labels, sample_gt, n_pos, bitmaps, img_hw=None, loss_weight=1.0, dlogits=None, want_avg=False, out=None, num_classes=None):
+    """Mask targets and the mask loss of the whole batch (mtp_mask_loss): two launches, no host synchronisation.  mask_preds (images * S, K, M, M)
+    f32 logits; boxes (images * S, 4); labels (images * S) int64 the class channel of each slot, or None (class-agnostic: channel 0); sample_gt
+    (images, S) int64 rows of bitmaps (G, H, W) uint8; n_pos (images) int64 on the device; img_hw (images, 2) int64 or None.
+    dlogits: a buffer like mask_preds for the gradient, every element stored.  num_classes: the labels name the first num_classes of the K
+    channels (a GEMM output padded to 8 columns); a slot with a label beyond them is padding.
+    -> dict(loss (1), targets (images * S, M, M) uint8, slot_loss (images * S), target_avg (like targets, f32) when want_avg)"""
+    if mask_preds.dtype != torch.float32 or mask_preds.dim() != 4 or mask_preds.shape[2] != mask_preds.shape[3] or not mask_preds.is_contiguous():
+        raise TypeError("mask_loss: mask_preds must be contiguous float32 of shape (slots, K, M, M)")
+    R, K, M, _ = mask_preds.shape
+    classes = K if num_classes is None else int(num_classes)
+    if not 1 <= classes <= K:
+        raise ValueError("mask_loss: num_classes in 1 .. %d, the channels of mask_preds" % K)
+    if sample_gt.dim() != 2 or sample_gt.numel() != R or R == 0:
+        raise ValueError("mask_loss: sample_gt (images, S) with images * S = %d slots > 0" % R)
+    images, S = sample_gt.shape
+    _check_boxes("mask_loss", boxes, 4)
+    if boxes.shape[0] != R:
+        raise ValueError("mask_loss: one box per slot")
+    if bitmaps.dtype != torch.uint8 or bitmaps.dim() != 3 or not bitmaps.is_contiguous():
+        raise TypeError("mask_loss: bitmaps must be contiguous uint8 of shape (G, H, W)")
+    G, H, W = bitmaps.shape
+    for t, shape in ((sample_gt, (images, S)), (n_pos, (images,))) + (() if labels is None else ((labels, (R,)),)) + (() if img_hw is None else ((img_hw, (images, 2)),)):
+        if t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise TypeError("mask_loss: sample_gt (images, S), n_pos (images), labels (slots) and img_hw (images, 2) are contiguous int64")
+    if dlogits is not None and (dlogits.dtype != torch.float32 or tuple(dlogits.shape) != tuple(mask_preds.shape) or not dlogits.is_contiguous()):
+        raise TypeError("mask_loss: dlogits has the layout of mask_preds")
+    if H < 1 or W < 1:
+        raise ValueError("mask_loss: the bitmaps have at least one pixel")
+    dev = mask_preds.device
+    if out is None:
+        out = dict(loss=_scratch((1,), dev, torch.float32), targets=_scratch((R, M, M), dev, torch.uint8), slot_loss=_scratch((R,), dev, torch.float32))
+        if want_avg:
+            out["target_avg"] = _scratch((R, M, M), dev, torch.float32)
+    avg = out.get("target_avg")
+    assert tuple(out["loss"].shape) == (1,) and tuple(out["targets"].shape) == (R, M, M) and out["targets"].dtype == torch.uint8
+    assert tuple(out["slot_loss"].shape) == (R,) and (avg is None or tuple(avg.shape) == (R, M, M))
+    check(lib().mtp_mask_loss(_f32(mask_preds), classes, K, M, _f32(boxes), _p(labels), _p(sample_gt), _p(n_pos), images, S, _p(bitmaps) if G else None, G, H, W,
+                              _p(img_hw), float(loss_weight), _p(out["targets"]), _p(avg), _f32(out["slot_loss"]), _f32(out["loss"]), _p(dlogits), _s()),
+          "mtp_mask_loss")
+    return out
+
+
+def mask_paste(mask_preds, labels, boxes, img_h, img_w, threshold=0.5, activate=True, out=None, values=None):
+    """_do_paste_mask(skip_empty=False) and the threshold in one launch: mask_preds (N > 0, K, M, M) f32, labels (N) int64 or None (channel 0),
+    boxes (N, 4) -> (N, img_h, img_w) bool (threshold >= 0) or uint8 (threshold < 0: value * 255).  values: an (N, img_h, img_w) f32 buffer for
+    the sampled values."""
+    if mask_preds.dtype != torch.float32 or mask_preds.dim() != 4 or mask_preds.shape[2] != mask_preds.shape[3] or not mask_preds.is_contiguous():
+        raise TypeError("mask_paste: mask_preds must be contiguous float32 of shape (N, K, M, M)")
+    N, K, M, _ = mask_preds.shape
+    _check_boxes("mask_paste", boxes, 4)
+    if N == 0 or boxes.shape[0] != N or img_h < 1 or img_w < 1:
+        raise ValueError("mask_paste: N > 0 instances with one box each, and an image of at least one pixel")
+    if labels is not None and (labels.dtype != torch.int64 or tuple(labels.shape) != (N,) or not labels.is_contiguous()):
+        raise TypeError("mask_paste: labels must be contiguous int64 of shape (N,)")
+    shape = (N, int(img_h), int(img_w))
+    out = _scratch(shape, mask_preds.device, torch.uint8) if out is None else out
+    assert out.dtype == torch.uint8 and tuple(out.shape) == shape and out.is_contiguous()
+    assert values is None or (values.dtype == torch.float32 and tuple(values.shape) == shape and values.is_contiguous())
+    check(lib().mtp_mask_paste(_f32(mask_preds), K, M, _p(labels), _f32(boxes), N, shape[1], shape[2], float(threshold), int(bool(activate)), _p(out),
+                               _p(values), _s()), "mtp_mask_paste")
+    return out.view(torch.bool) if threshold >= 0 else out
