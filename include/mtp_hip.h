@@ -871,6 +871,55 @@ int mtp_mask_loss(const float* mask_preds, int64_t num_classes, int64_t channels
 int mtp_mask_paste(const float* mask_preds, int64_t num_classes, int mask_size, const int64_t* labels, const float* boxes, int64_t N, int64_t img_h,
                    int64_t img_w, float threshold, int activate, uint8_t* out, float* values, mtp_stream_t stream);
 
+/* ---- the box half of Mask R-CNN (csrc/hbox_head.hip): DeltaXYWHBBoxCoder (mmdet 3.x bbox2delta / delta2bbox), targets + loss of the horizontal RPN,
+ * its proposals, targets + loss and per-class prediction of the per-class 2-FC bbox head.  f32, int64 indices, no float atomics, two calls on the same
+ * inputs give the same bits.  Boxes are x1, y1, x2, y2; every (n, 4) box array is 16-byte aligned.  means, stds: 4 HOST floats each, stds > 0.  L1 has
+ * the gradient sign(pred - target), 0 at equality. ---- */
+/* priors (n, 4), gts (n, 4) -> deltas (n, 4) = ((dx, dy, log dw, log dh) - means) / stds */
+int mtp_hbox_delta_encode(const float* priors, const float* gts, const float* means, const float* stds, int64_t n, float* deltas, mtp_stream_t stream);
+/* priors (n, 4), deltas (n, 4) -> boxes (n, 4); dw, dh clamped to +-|log(wh_ratio_clip)|, wh_ratio_clip > 0.  max_shapes (images, 2) f32 (h, w) on the
+ * device, or NULL (then image_ids NULL and images 0): x is clipped to [0, w] and y to [0, h] of image image_ids[row] (int64 on the device; NULL: image
+ * 0); a row whose image is out of range is not clipped. */
+int mtp_hbox_delta_decode(const float* priors, const float* deltas, const float* means, const float* stds, float wh_ratio_clip, int64_t n,
+                          const float* max_shapes, const int64_t* image_ids, int64_t images, float* boxes, mtp_stream_t stream);
+int64_t mtp_hrpn_loss_workspace_bytes(int64_t images, int64_t samples);
+/* mtp_rpn_loss with four deltas (reg channel a * 4 + j), horizontal gts (K, 4) and L1 in place of SmoothL1: per sampled anchor the sigmoid BCE of the
+ * logit against 1 / 0 and, on positives, L1 of the four deltas against the encode of (prior, gt); loss_cls / loss_bbox (num_levels) = weight * (sum
+ * over the level) / avg_factor, avg_factor = sum (n_pos + n_neg) read on the device; the gradients of their total are stored at the sampled anchors
+ * of the caller's zeroed maps.  Two launches.  workspace: mtp_hrpn_loss_workspace_bytes(images, S). */
+int mtp_hrpn_loss(const mtp_rpn_level* levels, int num_levels, int64_t A, const float* priors, int64_t num_priors, const float* gts, int64_t K,
+                  const int64_t* samples, const int64_t* sample_gt, const int64_t* n_pos, const int64_t* n_neg, int64_t images, int64_t S,
+                  const float* means, const float* stds, float cls_weight, float bbox_weight, float* loss_cls, float* loss_bbox, void* workspace,
+                  int64_t workspace_bytes, mtp_stream_t stream);
+/* keep (images, T) as mtp_rpn_proposals takes it.  Per entry: scores = sigmoid(logit), boxes (., 4) = decode clipped to img_shapes[image] (images, 2)
+ * f32 (h, w) on the device, level_ids, valid = w > min_bbox_size && h > min_bbox_size of the CLIPPED box.  An index out of range: zeros, not valid.
+ * One launch. */
+int mtp_hrpn_proposals(const mtp_rpn_level* levels, int num_levels, int64_t A, const float* priors, int64_t num_priors, const int64_t* keep,
+                       int64_t images, const float* means, const float* stds, float wh_ratio_clip, const float* img_shapes, float min_bbox_size,
+                       float* scores, float* boxes, int64_t* level_ids, uint8_t* valid, mtp_stream_t stream);
+/* the regression target of mtp_hroi_loss: 1.0 in all four columns (instance_segmentation/base_bbox_head.py as written), or encode(roi, gt) (mmdet) */
+enum mtp_hroi_target { MTP_HROI_TARGET_ONES = 0, MTP_HROI_TARGET_ENCODED = 1 };
+int64_t mtp_hroi_loss_workspace_bytes(int64_t images, int64_t samples);
+/* Targets and both losses of the per-class bbox head, forward and backward, two launches; the slot layout of mtp_roi_loss: row b * S + j, n_pos[b]
+ * positives, then n_neg[b] negatives, then padding; images * S < 2^31.  cls_score (images S, ld_cls): num_classes + 1 logits per row; bbox_pred
+ * (images S, ld_reg): 4 * num_classes deltas, class k in columns 4 k .. 4 k + 3, ld_reg a multiple of 4 and the base 16-byte aligned; rois (images
+ * S, 4); gts (num_gts, 4), gt_labels (num_gts); sample_gt (images, S).  Label = the gt's on positives, num_classes on negatives; a positive whose
+ * gt row or label lies outside its range is padding (no term, zero gradients; it still counts in R_total).  losses[0] = cls_weight * sum CE /
+ * max(R_total, 1); losses[1] = bbox_weight * sum over the positives of L1(bbox_pred[row, 4 label .. 4 label + 3], target) / R_total; losses[2] =
+ * top-1 accuracy in percent; R_total = sum (n_pos + n_neg) read on the device, and with R_total = 0 everything is 0.  dcls (rows, num_classes + 1)
+ * and the DENSE dreg (rows, 4 num_classes), both or neither, in the layout of their inputs: every row and every class column is stored, zeros
+ * included.  One wave per row, any num_classes < 65536.  workspace: mtp_hroi_loss_workspace_bytes(images, S). */
+int mtp_hroi_loss(const float* cls_score, int64_t ld_cls, const float* bbox_pred, int64_t ld_reg, int64_t num_classes, const float* rois,
+                  const float* gts, const int64_t* gt_labels, int64_t num_gts, const int64_t* sample_gt, const int64_t* n_pos, const int64_t* n_neg,
+                  int64_t images, int64_t S, const float* means, const float* stds, int target_mode, float cls_weight, float bbox_weight, float* losses,
+                  float* dcls, float* dreg, void* workspace, int64_t workspace_bytes, mtp_stream_t stream);
+/* rois (R, 5): image, x1, y1, x2, y2.  Per RoI: scores (R, num_classes) = softmax without the background column; boxes (R, num_classes, 4) = decode
+ * of the RoI with each class's four deltas, clipped to img_shapes[image] (images, 2) f32 (h, w), then times inv_scale[image] (images, 2) f32 (1 / sx,
+ * 1 / sy) when non-NULL; flags (R, num_classes) bytes = score > score_thr.  A RoI that names no image: zero boxes, no flags.  One launch. */
+int mtp_hroi_predict(const float* cls_score, int64_t ld_cls, const float* bbox_pred, int64_t ld_reg, int64_t num_classes, const float* rois, int64_t R,
+                     const float* means, const float* stds, float wh_ratio_clip, const float* img_shapes, const float* inv_scale, int64_t images,
+                     float score_thr, float* scores, float* boxes, uint8_t* flags, mtp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,10 +56,10 @@ from .evaluation import Accuracy, DOTAMetric, IoUMetric, eval_rbbox_map  # noqa:
 from .ops_box import batched_nms, bbox_overlaps, box_iou_rotated, nms, nms_rotated  # noqa: F401
 from .task_modules import (AnchorGenerator, AssignResult, BboxOverlaps2D, MidpointOffsetCoder, MTP_RD_MaxIoUAssigner, MaxIoUAssigner,  # noqa: F401
                            RandomSampler, RBbox2HBboxOverlaps2D, RBboxOverlaps2D)
-from .task_modules import DeltaXYWHTRBBoxCoder  # noqa: F401
-from .dense_heads import OrientedRPNHead  # noqa: F401
+from .task_modules import DeltaXYWHBBoxCoder, DeltaXYWHTRBBoxCoder  # noqa: F401
+from .dense_heads import OrientedRPNHead, RPNHead  # noqa: F401
 from .ops_roi import RoIAlign, RoIAlignRotated  # noqa: F401
 from .roi_extractors import RotatedSingleRoIExtractor, SingleRoIExtractor  # noqa: F401
-from .roi_heads import FCNMaskHead, MaskRoIHead, Shared2FCBBoxHead, StandardRoIHead  # noqa: F401
+from .roi_heads import FCNMaskHead, HBoxRoIHead, HBoxShared2FCBBoxHead, MaskRoIHead, Shared2FCBBoxHead, StandardRoIHead  # noqa: F401
 
 __version__ = "0.6.2"      # = mtp_version() of libmtp_hip.so ("mtp_hip 0.6.2 (gfx950)"): the round of the build

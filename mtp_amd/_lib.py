@@ -39,6 +39,9 @@ ASSIGN_BOX, ASSIGN_RBOX2HBOX, ASSIGN_ROTATED = 0, 1, 2
 DET_MAX_THRS, DET_MAX_CLASSES, DET_AP_POINTS = 8, 4096, 11
 DET_AP_11POINTS, DET_AP_AREA = 0, 1
 
+# enum mtp_hroi_target (mtp_hroi_loss, csrc/hbox_head.hip)
+HROI_TARGET_ONES, HROI_TARGET_ENCODED = 0, 1
+
 # enum mtp_fuse_policy (mtp_fuse_pair_fwd / _bwd)
 FUSE_CONCAT, FUSE_SUM, FUSE_DIFF, FUSE_ABS_DIFF = 0, 1, 2, 3
 
@@ -255,6 +258,14 @@ SIGNATURES = {
     "mtp_roi_align_bwd": (i32, [C.POINTER(RoiLevel), i32, i64, i64, p, p, p, p, i64, i64, i32, i32, i32, f32, i32, p]),
     "mtp_mask_loss": (i32, [p, i64, i64, i32, p, p, p, p, i64, i64, p, i64, i64, i64, p, f32, p, p, p, p, p, p]),
     "mtp_mask_paste": (i32, [p, i64, i32, p, p, i64, i64, i64, f32, i32, p, p, p]),
+    "mtp_hbox_delta_encode": (i32, [p, p, C.POINTER(f32), C.POINTER(f32), i64, p, p]),
+    "mtp_hbox_delta_decode": (i32, [p, p, C.POINTER(f32), C.POINTER(f32), f32, i64, p, p, i64, p, p]),
+    "mtp_hrpn_loss_workspace_bytes": (i64, [i64, i64]),
+    "mtp_hrpn_loss": (i32, [C.POINTER(RpnLevel), i32, i64, p, i64, p, i64, p, p, p, p, i64, i64, C.POINTER(f32), C.POINTER(f32), f32, f32, p, p, p, i64, p]),
+    "mtp_hrpn_proposals": (i32, [C.POINTER(RpnLevel), i32, i64, p, i64, p, i64, C.POINTER(f32), C.POINTER(f32), f32, p, f32, p, p, p, p, p]),
+    "mtp_hroi_loss_workspace_bytes": (i64, [i64, i64]),
+    "mtp_hroi_loss": (i32, [p, i64, p, i64, i64, p, p, p, i64, p, p, p, i64, i64, C.POINTER(f32), C.POINTER(f32), i32, f32, f32, p, p, p, p, i64, p]),
+    "mtp_hroi_predict": (i32, [p, i64, p, i64, i64, p, i64, C.POINTER(f32), C.POINTER(f32), f32, p, p, i64, f32, p, p, p, p]),
     "mtp_version": (C.c_char_p, []),
     "mtp_stream_create_low_priority": (i32, [p]),
     "mtp_stream_create_cu_mask": (i32, [p, i32, p]),

@@ -14,31 +14,18 @@
 // The decoded quadrilateral c0, c1, -c0, -c1 scaled to a common diagonal is a rectangle centred on (gx, gy) with edges c1 - c0 and c1 + c0, so the
 // rotated box is a closed form: no minimum-area-rectangle search.  Contraction is off: tests/rpn_ref.py restates the same operations in the same order.
 #include "common.h"
+#include "rpn_levels.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kL = MTP_RPN_MAX_LEVELS;
 constexpr float kPi = 3.14159265358979323846f;
 constexpr float kMaxRatio = 4.135166556742356f;      // |log(16 / 1000)|
 
 struct Codec {
     float mean[6], stdv[6];
 };
-struct Level {
-    const float* cls;
-    const float* reg;
-    float* dcls;
-    float* dreg;
-    int64_t H, W, first, count, keep_first;
-    int64_t cs[4], rs[4];
-};
-struct Levels {
-    Level lv[kL];
-    int n;
-};
-
 // the circumscribed box of a rotated one as box_ops.hip has it; (ux, uy) and (vx, vy) are the half axes
 struct GtGeom {
     float x1, y1, x2, y2, ux, uy, vx, vy;
@@ -101,14 +88,6 @@ __device__ __forceinline__ void midpoint_decode(const float* p, const float* raw
     if (t >= kPi * 0.5f) t -= kPi;
     if (t < -(kPi * 0.5f)) t += kPi;
     r[0] = gx; r[1] = gy; r[2] = first ? l1 : l2; r[3] = first ? l2 : l1; r[4] = t;
-}
-
-__device__ __forceinline__ int level_of(const Levels& L, int64_t idx) {
-    int l = 0;
-#pragma unroll
-    for (int i = 1; i < kL; ++i)
-        if (i < L.n && idx >= L.lv[i].first) l = i;
-    return l;
 }
 
 // ------------------------------------------------------------------------------------------------------------------- anchors
@@ -287,34 +266,6 @@ bool make_codec(const float* means, const float* stds, Codec& k) {
         if (!(stds[i] > 0.0f)) return false;
     }
     return true;
-}
-
-// the levels tile the flat anchor order without gaps; every map pointer is there, the gradient maps both or neither on every level
-bool make_levels(const mtp_rpn_level* levels, int n, int64_t A, int64_t total, bool keeps, Levels& L, int64_t& T) {
-    if (!levels || n < 1 || n > kL || A < 1 || A > (1 << 16) || total < 1) return false;
-    int64_t first = 0;
-    T = 0;
-    const bool grads = levels[0].dcls != nullptr;
-    for (int i = 0; i < n; ++i) {
-        const mtp_rpn_level& s = levels[i];
-        if (!s.cls || !s.reg || s.H < 1 || s.W < 1 || s.H > (1 << 20) || s.W > (1 << 20)) return false;
-        if ((s.dcls != nullptr) != grads || (s.dreg != nullptr) != grads) return false;
-        Level& d = L.lv[i];
-        d.cls = s.cls; d.reg = s.reg; d.dcls = s.dcls; d.dreg = s.dreg;
-        d.H = s.H; d.W = s.W; d.first = first; d.count = s.H * s.W * A;
-        d.keep_first = T;
-        if (keeps && (s.keep_count < 0 || s.keep_count > d.count)) return false;
-        for (int c = 0; c < 4; ++c) {
-            if (s.cls_stride[c] < 0 || s.reg_stride[c] < 0) return false;
-            d.cs[c] = s.cls_stride[c];
-            d.rs[c] = s.reg_stride[c];
-        }
-        first += d.count;
-        T += keeps ? s.keep_count : 0;
-    }
-    for (int i = n; i < kL; ++i) L.lv[i] = L.lv[n - 1];
-    L.n = n;
-    return first == total;
 }
 
 }  // namespace

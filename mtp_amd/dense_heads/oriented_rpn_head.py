@@ -44,6 +44,9 @@ class OrientedRPNHead(nn.Module):
     """OrientedRPNHead(in_channels, feat_channels=256, num_convs=1, anchor_generator, bbox_coder, loss_cls, loss_bbox, train_cfg, test_cfg,
     precision='fp32').  State dict: rpn_conv / rpn_cls / rpn_reg .weight / .bias.  One class, sigmoid scores."""
 
+    # what the horizontal head (rpn_head.RPNHead) has otherwise: the deltas per anchor, the columns of a gt box, the scope of the coder's name
+    DELTAS, BOX_DIM, CODER_SCOPES, CODER_NAME = ops.RPN_DELTAS, 5, ("mmrotate.",), "the midpoint-offset coder (six deltas)"
+
     def __init__(self, in_channels, feat_channels=256, num_convs=1, num_classes=1,
                  anchor_generator=dict(type="AnchorGenerator", scales=[8], ratios=[0.5, 1.0, 2.0], strides=[4, 8, 16, 32, 64]),
                  bbox_coder=dict(type="MidpointOffsetCoder", target_means=[0.0] * 6, target_stds=[1.0, 1.0, 1.0, 1.0, 0.5, 0.5]),
@@ -60,8 +63,7 @@ class OrientedRPNHead(nn.Module):
             raise NotImplementedError("%s: reg_decoded_bbox is not built" % me)
         if _type(loss_cls, "mmdet.") != "CrossEntropyLoss" or not loss_cls.get("use_sigmoid", False) or loss_cls.get("class_weight") is not None:
             raise NotImplementedError("%s: loss_cls %r is not built (CrossEntropyLoss, use_sigmoid=True, no class weights)" % (me, loss_cls))
-        if _type(loss_bbox, "mmdet.") != "SmoothL1Loss" or not loss_bbox.get("beta", 1.0) > 0:
-            raise NotImplementedError("%s: loss_bbox %r is not built (SmoothL1Loss, beta > 0)" % (me, loss_bbox))
+        self._check_loss_bbox(loss_bbox)
         if loss_cls.get("reduction", "mean") != "mean" or loss_bbox.get("reduction", "mean") != "mean":
             raise NotImplementedError("%s: reduction other than 'mean' is not built" % me)
         if precision not in ("fp32", "bf16"):
@@ -70,9 +72,9 @@ class OrientedRPNHead(nn.Module):
             raise ValueError("%s: in_channels and feat_channels must be multiples of 8 (the GEMM operands' rows are 16-byte chunks)" % me)
         self.in_channels, self.feat_channels, self.num_convs, self.precision = int(in_channels), int(feat_channels), 1, precision
         self.prior_generator = _build(anchor_generator, "mmdet.")
-        self.bbox_coder = _build(bbox_coder, "mmrotate.")
-        if getattr(self.bbox_coder, "encode_size", None) != ops.RPN_DELTAS:
-            raise NotImplementedError("%s: the kernels are those of the midpoint-offset coder (six deltas)" % me)
+        self.bbox_coder = _build(bbox_coder, *self.CODER_SCOPES)
+        if getattr(self.bbox_coder, "encode_size", None) != self.DELTAS:
+            raise NotImplementedError("%s: the kernels are those of %s" % (me, self.CODER_NAME))
         A = set(self.prior_generator.num_base_priors)
         if len(A) != 1:
             raise ValueError("%s: every level has the same number of base anchors" % me)
@@ -88,11 +90,15 @@ class OrientedRPNHead(nn.Module):
             self.sampler = _build(self.train_cfg.get("sampler", dict(type="RandomSampler", num=256, pos_fraction=0.5, add_gt_as_proposals=False)), "mmdet.")
         self.rpn_conv = nn.Conv2d(self.in_channels, self.feat_channels, 3, padding=1)
         self.rpn_cls = nn.Conv2d(self.feat_channels, self.num_base_priors, 1)
-        self.rpn_reg = nn.Conv2d(self.feat_channels, self.num_base_priors * ops.RPN_DELTAS, 1)
+        self.rpn_reg = nn.Conv2d(self.feat_channels, self.num_base_priors * self.DELTAS, 1)
         for m in (self.rpn_conv, self.rpn_cls, self.rpn_reg):       # mmdet's init_cfg: Normal, std 0.01
             nn.init.normal_(m.weight, 0.0, 0.01)
             nn.init.constant_(m.bias, 0.0)
         self._inside, self._flat = {}, {}
+
+    def _check_loss_bbox(self, loss_bbox):
+        if _type(loss_bbox, "mmdet.") != "SmoothL1Loss" or not loss_bbox.get("beta", 1.0) > 0:
+            raise NotImplementedError("%s: loss_bbox %r is not built (SmoothL1Loss, beta > 0)" % (type(self).__name__, loss_bbox))
 
     # ------------------------------------------------------------------ the convolutions
     def _params(self):
@@ -121,13 +127,13 @@ class OrientedRPNHead(nn.Module):
         for (N, H, W), r in zip(c["geoms"], c["row0"]):
             m = RPNEngine.to_nchw(out[r:r + N * H * W], N, H, W)
             cls.append(m[:, :A].contiguous())
-            reg.append(m[:, A:A * (1 + ops.RPN_DELTAS)].contiguous())
+            reg.append(m[:, A:A * (1 + self.DELTAS)].contiguous())
         return cls, reg
 
     @torch.no_grad()
     def forward(self, feats):
-        """feats: one NCHW map per level -> (cls_scores [(N, A, H, W)], bbox_preds [(N, 6 A, H, W)]) f32.  No autograd graph: training goes
-        through loss_and_grads."""
+        """feats: one NCHW map per level -> (cls_scores [(N, A, H, W)], bbox_preds [(N, DELTAS A, H, W)]) f32 (six deltas here, four in RPNHead).
+        No autograd graph: training goes through loss_and_grads."""
         _, out, c, _, _, _ = self._maps(feats)
         return self._nchw(out, c)
 
@@ -157,7 +163,7 @@ class OrientedRPNHead(nn.Module):
         rows, gt_rows, n_pos, n_neg, gts, off, flat = [], [], [], [], [], 0, None
         for b, (gt, meta) in enumerate(zip(batch_gt_instances, batch_img_metas)):
             flat, inside = self._anchors(sizes, meta, device)
-            boxes = box_tensor(_get(gt, "rboxes", "bboxes")).detach().to(device=device, dtype=F32).reshape(-1, 5)
+            boxes = box_tensor(_get(gt, "rboxes", "bboxes")).detach().to(device=device, dtype=F32).reshape(-1, self.BOX_DIM)
             labels = _get(gt, "rlabels", "labels").to(device)
             res = self.assigner.assign(SimpleNamespace(priors=flat[inside]), SimpleNamespace(rboxes=boxes, rlabels=labels, bboxes=boxes, labels=labels))
             extra = {} if sample_inds is None else dict(pos_inds=sample_inds[b][0], neg_inds=sample_inds[b][1])
@@ -184,14 +190,17 @@ class OrientedRPNHead(nn.Module):
             dcls, dreg = [(g,) + m[1:] for g, m in zip(grads[0], cls)], [(g,) + m[1:] for g, m in zip(grads[1], reg)]
         elif grads is not None:            # one zeroed buffer in the layout of the buffer all maps are views of
             dcls, dreg = [(grads,) + m[1:] for m in cls], [(grads,) + m[1:] for m in reg]
-        lc, lb = ops.rpn_loss(cls, reg, sizes, self.num_base_priors, flat, gts, samples, sample_gt, n_pos, n_neg, self.bbox_coder.means, self.bbox_coder.stds,
-                              self.beta, self.cls_weight, self.bbox_weight, dcls, dreg)
+        lc, lb = self._loss_op(cls, reg, sizes, flat, gts, samples, sample_gt, n_pos, n_neg, dcls, dreg)
         return dict(loss_rpn_cls=list(lc.unbind(0)), loss_rpn_bbox=list(lb.unbind(0)))
+
+    def _loss_op(self, cls, reg, sizes, flat, gts, samples, sample_gt, n_pos, n_neg, dcls, dreg):
+        return ops.rpn_loss(cls, reg, sizes, self.num_base_priors, flat, gts, samples, sample_gt, n_pos, n_neg, self.bbox_coder.means, self.bbox_coder.stds,
+                            self.beta, self.cls_weight, self.bbox_weight, dcls, dreg)
 
     @torch.no_grad()
     def loss_by_feat(self, cls_scores, bbox_preds, batch_gt_instances, batch_img_metas, batch_gt_instances_ignore=None, generator=None, sample_inds=None,
                      return_grads=False):
-        """cls_scores [(N, A, H, W)], bbox_preds [(N, 6 A, H, W)]; gt_instances with .rboxes (K, 5) / .rlabels (K) (or .bboxes / .labels); img_metas
+        """cls_scores [(N, A, H, W)], bbox_preds [(N, DELTAS A, H, W)]; gt_instances with .rboxes (K, BOX_DIM) / .rlabels (K) (or .bboxes / .labels); img_metas
         with img_shape (and pad_shape).  sample_inds: per image (pos_inds, neg_inds) into the anchors inside the image, instead of the random draw.
         -> dict(loss_rpn_cls=[per level], loss_rpn_bbox=[per level]); with return_grads also the gradients of the sum of all losses with respect
         to cls_scores and bbox_preds, two lists of f32 maps"""
@@ -232,8 +241,7 @@ class OrientedRPNHead(nn.Module):
             keep.append(torch.sort(z, dim=1, descending=True, stable=True)[1][:, :k])
             counts.append(k)
         keep = torch.cat(keep, 1).contiguous()
-        scores, rboxes, hboxes, level_ids, valid = ops.rpn_proposals(cls, reg, sizes, self.num_base_priors, flat, keep, counts, self.bbox_coder.means,
-                                                                     self.bbox_coder.stds, min_size)
+        scores, rboxes, hboxes, level_ids, valid = self._proposals_op(cls, reg, sizes, flat, keep, counts, min_size, images, batch_img_metas, device)
         results = []
         for b in range(images):
             ok = valid[b].bool()
@@ -245,10 +253,14 @@ class OrientedRPNHead(nn.Module):
             results.append(SimpleNamespace(bboxes=rboxes[b][sel], scores=scores[b][sel], labels=torch.zeros(n, dtype=torch.int64, device=device), keep=sel))
         return results
 
+    def _proposals_op(self, cls, reg, sizes, flat, keep, counts, min_size, images, batch_img_metas, device):
+        """-> (scores, the boxes of the results, the axis-aligned boxes NMS runs on, level ids, valid)"""
+        return ops.rpn_proposals(cls, reg, sizes, self.num_base_priors, flat, keep, counts, self.bbox_coder.means, self.bbox_coder.stds, min_size)
+
     @torch.no_grad()
     def predict_by_feat(self, cls_scores, bbox_preds, batch_img_metas=None, cfg=None, rescale=False, with_nms=True):
-        """-> per image an object with bboxes (n, 5) cx cy w h theta, scores (n), labels (n) zeros, descending score; .keep: their positions in the
-        concatenated per-level top-nms_pre lists"""
+        """-> per image an object with bboxes (n, 5) cx cy w h theta (RPNHead: (n, 4) x1 y1 x2 y2), scores (n), labels (n) zeros, descending score;
+        .keep: their positions in the concatenated per-level top-nms_pre lists"""
         if rescale or not with_nms:
             raise NotImplementedError("%s: rescale and with_nms=False are not built (rpn_head.py asserts with_nms)" % type(self).__name__)
         cls = [ops.rpn_map_nchw(t.detach().to(F32).contiguous()) for t in cls_scores]

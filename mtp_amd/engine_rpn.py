@@ -2,8 +2,8 @@
 
 The weights are shared by the levels, so the levels' rows are stacked: one row per (level, image, y, x), level after level.  The 3x3 convolution is
 im2col3x3 + gemm_nt per level (bias from the GEMM epilogue); ReLU is bn_apply with identity statistics over all rows at once; the two 1x1
-convolutions are ONE gemm_nt over all rows with their 7 A output channels padded to a multiple of 8 columns: columns 0 .. A are the logits, A .. 7 A the
-deltas (anchor-major, six each).  ACT is f32 in 'fp32' mode and bf16 in 'bf16' mode; the logits, the deltas and every gradient are f32."""
+convolutions are ONE gemm_nt over all rows with their (1 + D) A output channels padded to a multiple of 8 columns: columns 0 .. A are the logits,
+A .. (1 + D) A the deltas (anchor-major, D each: six for the oriented head, four for the horizontal one; the widths are read off the weights).  ACT is f32 in 'fp32' mode and bf16 in 'bf16' mode; the logits, the deltas and every gradient are f32."""
 import torch
 
 from . import ops

@@ -1603,8 +1603,9 @@ def _rpn_codec(means, stds):
     return (C.c_float * 6)(*m), (C.c_float * 6)(*s)
 
 
-def _rpn_levels(cls_maps, reg_maps, sizes, A, images, dcls=None, dreg=None, keep_counts=None):
-    """-> (mtp_rpn_level array, number of anchors); every address a kernel can form from the strides lies inside its tensor"""
+def _rpn_levels(cls_maps, reg_maps, sizes, A, images, dcls=None, dreg=None, keep_counts=None, deltas=RPN_DELTAS):
+    """-> (mtp_rpn_level array, number of anchors); every address a kernel can form from the strides lies inside its tensor.  deltas: the reg
+    channels per anchor (6 for the oriented head, 4 for the horizontal one)"""
     n = len(sizes)
     if not 1 <= n <= RPN_MAX_LEVELS or len(cls_maps) != n or len(reg_maps) != n:
         raise ValueError("rpn: 1 .. %d levels, one cls and one reg map each" % RPN_MAX_LEVELS)
@@ -1624,9 +1625,9 @@ def _rpn_levels(cls_maps, reg_maps, sizes, A, images, dcls=None, dreg=None, keep
 
     for i, (H, W) in enumerate(sizes):
         lv = arr[i]
-        lv.cls, lv.reg = addr(cls_maps[i], A, H, W), addr(reg_maps[i], A * RPN_DELTAS, H, W)
+        lv.cls, lv.reg = addr(cls_maps[i], A, H, W), addr(reg_maps[i], A * deltas, H, W)
         if dcls is not None:
-            lv.dcls, lv.dreg = addr(dcls[i], A, H, W, cls_maps[i]), addr(dreg[i], A * RPN_DELTAS, H, W, reg_maps[i])
+            lv.dcls, lv.dreg = addr(dcls[i], A, H, W, cls_maps[i]), addr(dreg[i], A * deltas, H, W, reg_maps[i])
         lv.H, lv.W = H, W
         lv.keep_count = 0 if keep_counts is None else int(keep_counts[i])
         lv.cls_stride, lv.reg_stride = (C.c_int64 * 4)(*cls_maps[i][2]), (C.c_int64 * 4)(*reg_maps[i][2])
@@ -2017,3 +2018,190 @@ def mask_paste(mask_preds, labels, boxes, img_h, img_w, threshold=0.5, activate=
     check(lib().mtp_mask_paste(_f32(mask_preds), K, M, _p(labels), _f32(boxes), N, shape[1], shape[2], float(threshold), int(bool(activate)), _p(out),
                                _p(values), _s()), "mtp_mask_paste")
     return out.view(torch.bool) if threshold >= 0 else out
+
+
+# ------------------------------------------------------------------------------------------------ the box half of Mask R-CNN (csrc/hbox_head.hip)
+HBOX_DELTAS = 4
+HBOX_WH_RATIO_CLIP = 16 / 1000
+HROI_TARGET = {"reference": _lib.HROI_TARGET_ONES, "encoded": _lib.HROI_TARGET_ENCODED}
+
+
+def _hbox_codec(means, stds):
+    m, s = [float(v) for v in means], [float(v) for v in stds]
+    if len(m) != HBOX_DELTAS or len(s) != HBOX_DELTAS or min(s) <= 0:
+        raise ValueError("the delta-xywh coder takes 4 means and 4 positive stds")
+    return (C.c_float * 4)(*m), (C.c_float * 4)(*s)
+
+
+def _hbox_clip(wh_ratio_clip):
+    if not wh_ratio_clip > 0:
+        raise ValueError("wh_ratio_clip must be positive")
+    return float(wh_ratio_clip)
+
+
+def _hbox_table(name, t, images, what):
+    """a per-image (images, 2) f32 table on the device: (h, w) shapes or (1 / sx, 1 / sy) factors"""
+    if t.dtype != torch.float32 or tuple(t.shape) != (images, 2) or not t.is_cuda:
+        raise TypeError("%s: %s must be a float32 device tensor of shape (images, 2)" % (name, what))
+    return _f32(t)
+
+
+def hbox_delta_encode(priors, gts, means, stds, out=None):
+    """DeltaXYWHBBoxCoder encode (mmdet bbox2delta): priors (n, 4), gts (n, 4) -> deltas (n, 4)"""
+    _check_boxes("hbox_delta_encode", priors, 4)
+    _check_boxes("hbox_delta_encode", gts, 4)
+    n = priors.shape[0]
+    assert gts.shape[0] == n and n > 0
+    out = _scratch((n, 4), priors.device, torch.float32) if out is None else out
+    assert tuple(out.shape) == (n, 4)
+    m, s = _hbox_codec(means, stds)
+    check(lib().mtp_hbox_delta_encode(_f32(priors), _f32(gts), m, s, n, _f32(out), _s()), "mtp_hbox_delta_encode")
+    return out
+
+
+def hbox_delta_decode(priors, deltas, means, stds, max_shapes=None, image_ids=None, wh_ratio_clip=HBOX_WH_RATIO_CLIP, out=None):
+    """DeltaXYWHBBoxCoder decode (mmdet delta2bbox): priors (n, 4), deltas (n, 4) -> boxes (n, 4).  max_shapes: None (no clip) or an (images, 2)
+    f32 device table of (h, w); image_ids (n) int64: the image of each row (None: image 0).  One launch for the whole batch."""
+    _check_boxes("hbox_delta_decode", priors, 4)
+    _check_boxes("hbox_delta_decode", deltas, 4)
+    n = priors.shape[0]
+    assert deltas.shape[0] == n and n > 0
+    images = 0
+    if max_shapes is None:
+        if image_ids is not None:
+            raise ValueError("hbox_delta_decode: image_ids without max_shapes")
+    else:
+        images = max_shapes.shape[0]
+        _hbox_table("hbox_delta_decode", max_shapes, images, "max_shapes")
+        if image_ids is not None and (image_ids.dtype != torch.int64 or tuple(image_ids.shape) != (n,)):
+            raise TypeError("hbox_delta_decode: image_ids must be int64 of shape (n,)")
+    out = _scratch((n, 4), priors.device, torch.float32) if out is None else out
+    assert tuple(out.shape) == (n, 4)
+    m, s = _hbox_codec(means, stds)
+    check(lib().mtp_hbox_delta_decode(_f32(priors), _f32(deltas), m, s, _hbox_clip(wh_ratio_clip), n, _f32(max_shapes), _p(image_ids), images, _f32(out),
+                                      _s()), "mtp_hbox_delta_decode")
+    return out
+
+
+def hrpn_loss(cls_maps, reg_maps, sizes, A, priors, gts, samples, sample_gt, n_pos, n_neg, means, stds, cls_weight=1.0, bbox_weight=1.0, dcls=None,
+              dreg=None, loss_cls=None, loss_bbox=None):
+    """Targets and loss of the horizontal RPN for the whole batch (mtp_hrpn_loss): rpn_loss with four deltas per anchor, gts (K, 4) and L1.
+    dcls / dreg: gradient maps in the maps' layout, ZEROED by the caller (both or neither).  -> (loss_cls (levels), loss_bbox (levels)) f32"""
+    _check_boxes("hrpn_loss", priors, 4)
+    _check_boxes("hrpn_loss", gts, 4)
+    images, S = samples.shape
+    if (dcls is None) != (dreg is None):
+        raise ValueError("hrpn_loss: dcls and dreg come together")
+    arr, total = _rpn_levels(cls_maps, reg_maps, sizes, A, images, dcls, dreg, deltas=HBOX_DELTAS)
+    if priors.shape[0] != total:
+        raise ValueError("hrpn_loss: %d priors for %d anchors" % (priors.shape[0], total))
+    for t, shape in ((samples, (images, S)), (sample_gt, (images, S)), (n_pos, (images,)), (n_neg, (images,))):
+        if t.dtype != torch.int64 or tuple(t.shape) != shape:
+            raise TypeError("hrpn_loss: samples, sample_gt (images, S) and n_pos, n_neg (images) are int64")
+    dev, n = priors.device, len(sizes)
+    loss_cls = _scratch((n,), dev, torch.float32) if loss_cls is None else loss_cls
+    loss_bbox = _scratch((n,), dev, torch.float32) if loss_bbox is None else loss_bbox
+    assert tuple(loss_cls.shape) == tuple(loss_bbox.shape) == (n,)
+    wb = lib().mtp_hrpn_loss_workspace_bytes(images, S)
+    ws = _scratch((wb // 4,), dev, torch.float32)
+    m, s = _hbox_codec(means, stds)
+    K = gts.shape[0]
+    check(lib().mtp_hrpn_loss(arr, n, A, _f32(priors), total, _f32(gts) if K else None, K, _p(samples), _p(sample_gt), _p(n_pos), _p(n_neg), images, S, m, s,
+                              float(cls_weight), float(bbox_weight), _f32(loss_cls), _f32(loss_bbox), _p(ws), wb, _s()), "mtp_hrpn_loss")
+    return loss_cls, loss_bbox
+
+
+def hrpn_proposals(cls_maps, reg_maps, sizes, A, priors, keep, keep_counts, means, stds, img_shapes, min_bbox_size=0.0,
+                   wh_ratio_clip=HBOX_WH_RATIO_CLIP, out=None):
+    """keep (images, T) int64 as rpn_proposals takes it; img_shapes (images, 2) f32 (h, w) on the device.
+    -> scores (images, T) f32, boxes (images, T, 4) clipped to the image, level_ids (images, T) int64, valid (images, T) uint8.  One launch."""
+    _check_boxes("hrpn_proposals", priors, 4)
+    images, T = keep.shape
+    if keep.dtype != torch.int64 or T != sum(int(k) for k in keep_counts) or T == 0:
+        raise TypeError("hrpn_proposals: keep must be int64 of shape (images, sum(keep_counts) > 0)")
+    arr, total = _rpn_levels(cls_maps, reg_maps, sizes, A, images, keep_counts=keep_counts, deltas=HBOX_DELTAS)
+    if priors.shape[0] != total:
+        raise ValueError("hrpn_proposals: %d priors for %d anchors" % (priors.shape[0], total))
+    shapes = _hbox_table("hrpn_proposals", img_shapes, images, "img_shapes")
+    dev = priors.device
+    if out is None:
+        out = (_scratch((images, T), dev, torch.float32), _scratch((images, T, 4), dev, torch.float32), _scratch((images, T), dev, torch.int64),
+               _scratch((images, T), dev, torch.uint8))
+    scores, boxes, level_ids, valid = out
+    assert tuple(scores.shape) == tuple(level_ids.shape) == tuple(valid.shape) == (images, T) and level_ids.dtype == torch.int64 and valid.dtype == torch.uint8
+    assert tuple(boxes.shape) == (images, T, 4)
+    m, s = _hbox_codec(means, stds)
+    check(lib().mtp_hrpn_proposals(arr, len(sizes), A, _f32(priors), total, _p(keep), images, m, s, _hbox_clip(wh_ratio_clip), shapes, float(min_bbox_size),
+                                   _f32(scores), _f32(boxes), _p(level_ids), _p(valid), _s()), "mtp_hrpn_proposals")
+    return scores, boxes, level_ids, valid
+
+
+def _hroi_reg_rows(name, t, num_classes):
+    """(rows, >= 4 K) f32 rows whose pitch is a multiple of 4 elements and whose base is 16-byte aligned: class k is one 16-byte access"""
+    ptr, ld = _roi_rows(name, t, 4 * num_classes)
+    if ld % 4 or ptr % 16:
+        raise ValueError("%s: the 4 K deltas of a row start on 16 bytes (pitch a multiple of 4 floats)" % name)
+    return ptr, ld
+
+
+def hroi_loss(cls_score, bbox_pred, num_classes, rois, gts, gt_labels, sample_gt, n_pos, n_neg, means, stds, reg_target="reference", cls_weight=1.0,
+              bbox_weight=1.0, dcls=None, dreg=None, losses=None):
+    """Targets and losses of the per-class bbox head for the whole batch (mtp_hroi_loss): two launches, no host synchronisation.  cls_score (images *
+    S, num_classes + 1) and bbox_pred (images * S, 4 * num_classes): rows of a wider buffer are fine; rois (images * S, 4); gts (G, 4), gt_labels (G);
+    sample_gt (images, S), n_pos, n_neg (images) int64.  reg_target: 'reference' (all ones, instance_segmentation/base_bbox_head.py as written) or
+    'encoded' (mmdet: encode(roi, gt)).  dcls / dreg: the gradients in the layout of their inputs, dreg dense: every class column of every row is
+    stored.  -> losses (3) f32: loss_cls, loss_bbox, acc in percent"""
+    images, S = sample_gt.shape
+    R = images * S
+    _check_boxes("hroi_loss", rois, 4)
+    _check_boxes("hroi_loss", gts, 4)
+    if reg_target not in HROI_TARGET:
+        raise ValueError("hroi_loss: reg_target is 'reference' or 'encoded', got %r" % (reg_target,))
+    if R == 0 or rois.shape[0] != R or cls_score.shape[0] != R or bbox_pred.shape[0] != R:
+        raise ValueError("hroi_loss: %d rows for %d x %d slots" % (rois.shape[0], images, S))
+    G = gts.shape[0]
+    for t, shape in ((sample_gt, (images, S)), (n_pos, (images,)), (n_neg, (images,)), (gt_labels, (G,))):
+        if t.dtype != torch.int64 or tuple(t.shape) != shape:
+            raise TypeError("hroi_loss: sample_gt (images, S), n_pos, n_neg (images) and gt_labels (G) are int64")
+    (pc, ldc), (pr, ldr) = _roi_rows("hroi_loss", cls_score, num_classes + 1), _hroi_reg_rows("hroi_loss", bbox_pred, num_classes)
+    if (dcls is None) != (dreg is None):
+        raise ValueError("hroi_loss: dcls and dreg come together")
+    pdc = pdr = None
+    if dcls is not None:
+        (pdc, a), (pdr, b) = _roi_rows("hroi_loss", dcls, num_classes + 1), _hroi_reg_rows("hroi_loss", dreg, num_classes)
+        if a != ldc or b != ldr or dcls.shape[0] != R or dreg.shape[0] != R:
+            raise ValueError("hroi_loss: a gradient has the layout of its input")
+    dev = rois.device
+    losses = _scratch((3,), dev, torch.float32) if losses is None else losses
+    assert tuple(losses.shape) == (3,)
+    wb = lib().mtp_hroi_loss_workspace_bytes(images, S)
+    ws = _scratch((wb // 4,), dev, torch.float32)
+    m, s = _hbox_codec(means, stds)
+    check(lib().mtp_hroi_loss(pc, ldc, pr, ldr, int(num_classes), _f32(rois), _f32(gts) if G else None, _p(gt_labels) if G else None, G, _p(sample_gt),
+                              _p(n_pos), _p(n_neg), images, S, m, s, HROI_TARGET[reg_target], float(cls_weight), float(bbox_weight), _f32(losses), pdc, pdr,
+                              _p(ws), wb, _s()), "mtp_hroi_loss")
+    return losses
+
+
+def hroi_predict(cls_score, bbox_pred, num_classes, rois, means, stds, img_shapes, inv_scale=None, score_thr=0.0, wh_ratio_clip=HBOX_WH_RATIO_CLIP,
+                 out=None):
+    """rois (R, 5): image, x1, y1, x2, y2.  Per RoI the softmax scores (R, num_classes), the num_classes decoded boxes (R, num_classes, 4) clipped to
+    img_shapes[image] (images, 2) f32 (h, w) and multiplied by inv_scale[image] (images, 2) f32 (1 / sx, 1 / sy) when given, and the score >
+    score_thr flags (R, num_classes) uint8: one launch"""
+    _check_boxes("hroi_predict", rois, 5)
+    R = rois.shape[0]
+    if R == 0 or cls_score.shape[0] != R or bbox_pred.shape[0] != R:
+        raise ValueError("hroi_predict: R > 0 rows of scores, deltas and rois")
+    (pc, ldc), (pr, ldr) = _roi_rows("hroi_predict", cls_score, num_classes + 1), _hroi_reg_rows("hroi_predict", bbox_pred, num_classes)
+    images = img_shapes.shape[0]
+    shapes = _hbox_table("hroi_predict", img_shapes, images, "img_shapes")
+    inv = None if inv_scale is None else _hbox_table("hroi_predict", inv_scale, images, "inv_scale")
+    dev = rois.device
+    if out is None:
+        out = (_scratch((R, num_classes), dev, torch.float32), _scratch((R, num_classes, 4), dev, torch.float32), _scratch((R, num_classes), dev, torch.uint8))
+    scores, boxes, flags = out
+    assert tuple(scores.shape) == tuple(flags.shape) == (R, num_classes) and tuple(boxes.shape) == (R, num_classes, 4) and flags.dtype == torch.uint8
+    m, s = _hbox_codec(means, stds)
+    check(lib().mtp_hroi_predict(pc, ldc, pr, ldr, int(num_classes), _f32(rois), R, m, s, _hbox_clip(wh_ratio_clip), shapes, inv, images, float(score_thr),
+                                 _f32(scores), _f32(boxes), _p(flags), _s()), "mtp_hroi_predict")
+    return scores, boxes, flags

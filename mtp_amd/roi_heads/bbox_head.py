@@ -19,6 +19,9 @@ F32 = torch.float32
 class Shared2FCBBoxHead(nn.Module):
     """State dict: shared_fcs.{0,1}.{weight,bias}, and with num_classes fc_cls.* (num_classes + 1 rows) and fc_reg.* (5 rows)."""
 
+    # what the per-class horizontal head (hbox_head.HBoxShared2FCBBoxHead) has otherwise, beside _check_regression and reg_width
+    DELTAS, BOX_TYPE, CODER_SCOPE, CODER_NAME = ops.ROI_DELTAS, "rbox", "mmrotate.", "the delta-xywht coder (five deltas)"
+
     def __init__(self, in_channels=256, fc_out_channels=1024, roi_feat_size=7, num_classes=None, num_shared_convs=0, num_shared_fcs=2, with_avg_pool=False,
                  with_cls=True, with_reg=True, predict_box_type="rbox", reg_class_agnostic=True, reg_decoded_bbox=False,
                  reg_predictor_cfg=dict(type="mmdet.Linear"), cls_predictor_cfg=dict(type="mmdet.Linear"),
@@ -32,11 +35,9 @@ class Shared2FCBBoxHead(nn.Module):
             raise NotImplementedError("%s: two shared fully connected layers and no shared convolutions are what is built" % me)
         if with_avg_pool or not with_cls or not with_reg:
             raise NotImplementedError("%s: with_avg_pool, with_cls=False and with_reg=False are not built" % me)
-        if not reg_class_agnostic:
-            raise NotImplementedError("%s: reg_class_agnostic=False is not built (the MTP configurations regress one box per RoI)" % me)
         if reg_decoded_bbox:
             raise NotImplementedError("%s: reg_decoded_bbox is not built" % me)
-        if predict_box_type != "rbox":
+        if predict_box_type != self.BOX_TYPE:
             raise NotImplementedError("%s: predict_box_type %r is not built" % (me, predict_box_type))
         for cfg in (reg_predictor_cfg, cls_predictor_cfg):
             if _strip(cfg, "mmdet.")["type"] != "Linear":
@@ -44,8 +45,7 @@ class Shared2FCBBoxHead(nn.Module):
         lc, lb = _strip(loss_cls, "mmdet."), _strip(loss_bbox, "mmdet.")
         if lc["type"] != "CrossEntropyLoss" or lc.get("use_sigmoid", False) or lc.get("use_mask", False) or lc.get("class_weight") is not None:
             raise NotImplementedError("%s: loss_cls %r is not built (softmax CrossEntropyLoss, no class weights)" % (me, loss_cls))
-        if lb["type"] != "SmoothL1Loss" or not lb.get("beta", 1.0) > 0:
-            raise NotImplementedError("%s: loss_bbox %r is not built (SmoothL1Loss, beta > 0)" % (me, loss_bbox))
+        self._check_regression(reg_class_agnostic, lb, loss_bbox)
         if lc.get("reduction", "mean") != "mean" or lb.get("reduction", "mean") != "mean":
             raise NotImplementedError("%s: reduction other than 'mean' is not built" % me)
         if precision not in ("fp32", "bf16"):
@@ -54,10 +54,10 @@ class Shared2FCBBoxHead(nn.Module):
             raise ValueError("%s: in_channels and fc_out_channels must be multiples of 8 (the GEMM operands' rows are 16-byte chunks)" % me)
         self.in_channels, self.fc_out_channels, self.roi_feat_size, self.precision = int(in_channels), int(fc_out_channels), int(roi_feat_size), precision
         self.roi_feat_area = self.roi_feat_size ** 2
-        self.reg_class_agnostic, self.reg_decoded_bbox, self.predict_box_type = True, False, "rbox"
-        self.bbox_coder = TASK_UTILS.build(_strip(bbox_coder, "mmrotate."))
-        if getattr(self.bbox_coder, "encode_size", None) != ops.ROI_DELTAS:
-            raise NotImplementedError("%s: the kernels are those of the delta-xywht coder (five deltas)" % me)
+        self.reg_class_agnostic, self.reg_decoded_bbox, self.predict_box_type = bool(reg_class_agnostic), False, self.BOX_TYPE
+        self.bbox_coder = TASK_UTILS.build(_strip(bbox_coder, self.CODER_SCOPE))
+        if getattr(self.bbox_coder, "encode_size", None) != self.DELTAS:
+            raise NotImplementedError("%s: the kernels are those of %s" % (me, self.CODER_NAME))
         self.cls_weight, self.bbox_weight, self.beta = float(lc.get("loss_weight", 1.0)), float(lb.get("loss_weight", 1.0)), float(lb.get("beta", 1.0))
         self.shared_fcs = nn.ModuleList([nn.Linear(self.in_channels * self.roi_feat_area, self.fc_out_channels),
                                          nn.Linear(self.fc_out_channels, self.fc_out_channels)])
@@ -70,12 +70,23 @@ class Shared2FCBBoxHead(nn.Module):
             if self.num_classes < 1:
                 raise ValueError("%s: num_classes >= 1" % me)
             self.fc_cls = nn.Linear(self.cls_last_dim, self.num_classes + 1)
-            self.fc_reg = nn.Linear(self.reg_last_dim, ops.ROI_DELTAS)
+            self.fc_reg = nn.Linear(self.reg_last_dim, self.reg_width(self.num_classes))
             nn.init.normal_(self.fc_cls.weight, 0.0, 0.01)      # mmdet's init_cfg: Normal, std 0.01 / 0.001
             nn.init.normal_(self.fc_reg.weight, 0.0, 0.001)
             nn.init.constant_(self.fc_cls.bias, 0.0)
             nn.init.constant_(self.fc_reg.bias, 0.0)
         self._images = {}
+
+    def _check_regression(self, reg_class_agnostic, lb, loss_bbox):
+        me = type(self).__name__
+        if not reg_class_agnostic:
+            raise NotImplementedError("%s: reg_class_agnostic=False is not built (the MTP configurations regress one box per RoI)" % me)
+        if lb["type"] != "SmoothL1Loss" or not lb.get("beta", 1.0) > 0:
+            raise NotImplementedError("%s: loss_bbox %r is not built (SmoothL1Loss, beta > 0)" % (me, loss_bbox))
+
+    def reg_width(self, num_classes):
+        """the rows of fc_reg"""
+        return self.DELTAS
 
     # ------------------------------------------------------------------ the layers
     def invalidate_weights(self):

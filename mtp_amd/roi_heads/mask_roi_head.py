@@ -1,7 +1,7 @@
 """MTP_IS_StandardRoIHead: the mask half of the reference's instance-segmentation RoI head (instance_segmentation/roi_head.py: init_mask_head,
 train_mask_forward, mask_loss, test_mask_generate_rois, test_mask_roi_feats, predict_mask; configured at mask_rcnn.py:56-68, 92-119):
 SingleRoIExtractor (RoIAlign 14, adaptive grid) -> FCNMaskHead -> the data set's 1x1 conv_logits -> mask targets + binary cross-entropy, and the
-paste at test time.  The horizontal box half (bbox_roi_extractor, bbox_head) is the next step and is not built: asking for it raises.
+paste at test time.  The horizontal box half (bbox_roi_extractor, bbox_head) is a class of its own, hbox_roi_head.HBoxRoIHead; asking this one for it raises.
 
 Training takes the positives in either of two forms: the reference's list of per-image sampling results (pos_priors, pos_assigned_gt_inds,
 pos_gt_labels), or the fixed-slot form of the oriented head -- S slots per image, the first n_pos[b] of them positives, n_pos on the device.  The

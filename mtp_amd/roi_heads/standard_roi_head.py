@@ -30,14 +30,14 @@ class StandardRoIHead(nn.Module):
         super().__init__()
         me = type(self).__name__
         if mask_roi_extractor is not None or mask_head is not None:
-            raise NotImplementedError("%s: the mask branch is not built" % me)
+            raise NotImplementedError("%s: %s" % (me, self.MASK_REFUSAL))
         if shared_head is not None:
             raise NotImplementedError("%s: a shared head is not built" % me)
         if bbox_roi_extractor is None or bbox_head is None:
             raise TypeError("%s: bbox_roi_extractor and bbox_head are needed" % me)
-        self.bbox_roi_extractor = bbox_roi_extractor if isinstance(bbox_roi_extractor, nn.Module) else MODELS.build(_strip(bbox_roi_extractor, "mmrotate."))
-        self.bbox_head = bbox_head if isinstance(bbox_head, nn.Module) else MODELS.build(dict(bbox_head))
-        if self.bbox_roi_extractor.out_channels != self.bbox_head.in_channels or self.bbox_roi_extractor.roi_layers[0].out_size != self.bbox_head.roi_feat_size:
+        self.bbox_roi_extractor = bbox_roi_extractor if isinstance(bbox_roi_extractor, nn.Module) else MODELS.build(_strip(bbox_roi_extractor, *self.SCOPES))
+        self.bbox_head = bbox_head if isinstance(bbox_head, nn.Module) else MODELS.build(_strip(bbox_head, *self.HEAD_SCOPES))
+        if self.bbox_roi_extractor.out_channels != self.bbox_head.in_channels or getattr(self.bbox_roi_extractor.roi_layers[0], self.ROI_SIZE) != self.bbox_head.roi_feat_size:
             raise ValueError("%s: the extractor's output is the bbox head's input" % me)
         self.train_cfg, self.test_cfg = (None if train_cfg is None else dict(train_cfg)), (None if test_cfg is None else dict(test_cfg))
         self.bbox_assigner = self.bbox_sampler = None
@@ -52,6 +52,9 @@ class StandardRoIHead(nn.Module):
             self.bbox_sampler = TASK_UTILS.build(dict(sampler, add_gt_as_proposals=False))
 
     with_bbox, with_mask, with_shared_head = True, False, False
+    # what the horizontal box half (hbox_roi_head.HBoxRoIHead) has otherwise: the columns of a box (cx cy w h theta; there x1 y1 x2 y2), the scopes
+    # stripped from the extractor's and the head's type, the RoI layer's attribute for its output size, the words of the mask refusal
+    BOX_DIM, SCOPES, HEAD_SCOPES, ROI_SIZE, MASK_REFUSAL = 5, ("mmrotate.",), (), "out_size", "the mask branch is not built"
 
     def invalidate_weights(self):
         """the parameters were written through raw pointers (see Shared2FCBBoxHead.invalidate_weights)"""
@@ -74,9 +77,9 @@ class StandardRoIHead(nn.Module):
         S = self.bbox_sampler.num
         rois, inds, gt_rows, n_pos, n_neg, gts, labels, off = [], [], [], [], [], [], [], 0
         for b, (res, gt) in enumerate(zip(rpn_results_list, batch_gt_instances)):
-            props = box_tensor(_get(res, "bboxes", "priors")).detach().to(F32).reshape(-1, 5)
+            props = box_tensor(_get(res, "bboxes", "priors")).detach().to(F32).reshape(-1, self.BOX_DIM)
             dev = props.device
-            boxes = box_tensor(_get(gt, "rboxes", "bboxes")).detach().to(device=dev, dtype=F32).reshape(-1, 5)
+            boxes = box_tensor(_get(gt, "rboxes", "bboxes")).detach().to(device=dev, dtype=F32).reshape(-1, self.BOX_DIM)
             lab = _get(gt, "rlabels", "labels").to(device=dev, dtype=torch.int64).reshape(-1)
             count = _opt(res, "count")
             if count is not None:      # padding rows: never drawn, and harmless to the IoU kernel
@@ -91,7 +94,7 @@ class StandardRoIHead(nn.Module):
             extra = {} if sample_inds is None else dict(pos_inds=sample_inds[b][0], neg_inds=sample_inds[b][1])
             sl = self.bbox_sampler.sample(AssignResult(K, gt_inds, None, None), generator=generator, **extra)
             n = props.shape[0]
-            rows = props[sl.inds.clamp(0, max(n - 1, 0))] if n else torch.zeros(S, 5, device=dev)
+            rows = props[sl.inds.clamp(0, max(n - 1, 0))] if n else torch.zeros(S, self.BOX_DIM, device=dev)
             rois.append(torch.cat([torch.full((S, 1), float(b), device=dev), rows], 1))
             inds.append(sl.inds)
             gt_rows.append(torch.where(sl.gt_inds >= 0, sl.gt_inds + off, sl.gt_inds))
@@ -125,7 +128,7 @@ class StandardRoIHead(nn.Module):
         return out.permute(0, 2, 1).reshape(out.shape[0], -1, P, P), s["rois"]
 
     def test_bbox_generate_roi(self, rpn_results_list):
-        proposals = [box_tensor(_get(r, "bboxes", "priors")).detach().to(F32).reshape(-1, 5) for r in rpn_results_list]
+        proposals = [box_tensor(_get(r, "bboxes", "priors")).detach().to(F32).reshape(-1, self.BOX_DIM) for r in rpn_results_list]
         rois = [torch.cat([p.new_full((p.shape[0], 1), float(b)), p], 1) for b, p in enumerate(proposals)]
         return proposals, torch.cat(rois).contiguous()
 
