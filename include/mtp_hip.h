@@ -746,6 +746,52 @@ int mtp_det_tpfp(const float* det_scores, const float* best_iou, const int64_t* 
 int mtp_det_ap(const uint8_t* flags, const int64_t* order, const int64_t* cls_start, const int64_t* num_gts, int64_t D, int64_t K, int T, int mode,
                const double* recall_points, float* ap, int64_t* num_dets, double* last_recall, double* recall, float* precision, mtp_stream_t stream);
 
+/* ---- the COCO-style metric of instance segmentation (csrc/coco_eval.hip; the reference's MTP_IS_Metric = mmdet's CocoMetric over pycocotools'
+ * COCOeval: computeIoU, evaluateImg, accumulate).  float64 arithmetic with contraction off and correctly rounded divisions, integer atomics only,
+ * two calls give the same bits.  Arrays named HOST are read on the host before the launch. ---- */
+#define MTP_COCO_MAX_THRS 16
+#define MTP_COCO_AREAS 4
+#define MTP_COCO_MAX_DET_LEVELS 4
+#define MTP_COCO_MAX_CLASSES 4096
+#define MTP_COCO_REC_THRS 101
+#define MTP_COCO_MAX_CELL_GTS 4096 /* gts of one (image, category): 64 lanes x 64 taken bits */
+typedef enum { MTP_COCO_BBOX = 0, MTP_COCO_SEGM = 1 } mtp_coco_kind;
+/* masks (N, HW) u8 (non-zero = set) -> words (N, ceil(HW / 64)): bit p of word w = pixel 64 w + p, the tail of the last word zero; areas (N),
+ * ZEROED BY THE CALLER: += the set pixels.  N >= 0, HW >= 1. */
+int mtp_mask_pack(const uint8_t* masks, int64_t N, int64_t HW, uint64_t* words, int64_t* areas, mtp_stream_t stream);
+/* n_img >= 1 images: detections [det_start[i], det_start[i + 1]) of the (D) tables, gts [gt_start[i], gt_start[i + 1]) of the (G) tables, the dense
+ * row-major (D_i, G_i) block at iou + out_start[i]; det_start / gt_start / out_start are HOST arrays of n_img + 1 entries starting at 0 with
+ * out_start[i + 1] - out_start[i] = D_i G_i <= out_numel.  MTP_COCO_BBOX: boxes (., 4) f32 x1, y1, x2, y2; maskApi.c's bbIou on x, y, w = x2 - x1,
+ * h = y2 - y1 in double: iw = fmin(dx + dw, gx + gw) - fmax(dx, gx), ih likewise, 0 unless both > 0, else i / (crowd ? da : da + ga - i).
+ * MTP_COCO_SEGM: words (., W) and areas from mtp_mask_pack; i = popcount of the AND, 0 when i = 0, else (double)i / (double)(crowd ? a_d :
+ * a_d + a_g - i); inter (same layout, may be NULL) receives i.  A pair of different labels is 0 unless agnostic.  Unused tables may be NULL. */
+int mtp_coco_iou(int kind, const float* det_boxes, const uint64_t* det_words, const int64_t* det_areas, const int64_t* det_labels, int64_t D,
+                 const float* gt_boxes, const uint64_t* gt_words, const int64_t* gt_areas, const int64_t* gt_labels, const uint8_t* gt_crowd, int64_t G,
+                 int64_t W, int agnostic, int64_t n_img, const int64_t* det_start, const int64_t* gt_start, const int64_t* out_start, double* iou,
+                 int64_t* inter, int64_t out_numel, mtp_stream_t stream);
+/* evaluateImg for every (cell, area range, threshold); cell = image * K + category, `cells` = images * K.  The (D) detection tables are in LIST ORDER:
+ * cell by cell, inside a cell by descending score (stable); det_cell_start (cells + 1).  det_row[p]: the offset of the detection's IoU row in
+ * iou; det_area f64.  The (G) gt tables are in any order: gt_col[g] the gt's column in its image's block, gt_crowd, gt_ig (A, G) = crowd or area
+ * outside range a; gt_order (A, G): per area range the gts cell by cell, inside a cell stably by gt_ig; gt_cell_start (cells + 1).  At most
+ * MTP_COCO_MAX_CELL_GTS gts per cell (the caller's check).  iou_thrs: T HOST doubles; area_rng: HOST (lo, hi) x 4, both ends inclusive.  Only
+ * the first max_det detections of a cell are matched, in order: the pick is the largest IoU >= min(t, 1 - 1e-10) among the non-ignored gts that are
+ * unmatched or crowd, the highest position among equal IoUs; else the same among the ignored ones.  matched / ignored (A, T, D) u8: ignored = the
+ * matched gt's gt_ig, or for an unmatched detection its area outside the range; both 0 past max_det.  rank (D) i32: the position inside the cell.  List positions past
+ * det_cell_start[cells] (no cell) get 0, 0 and rank 0.
+ * npig (K, A), ZEROED BY THE CALLER: += the gts with gt_ig = 0. */
+int mtp_coco_match(const double* iou, int64_t iou_numel, const int64_t* det_row, const double* det_area, const int64_t* det_cell_start, int64_t D,
+                   const int64_t* gt_order, const int64_t* gt_col, const uint8_t* gt_crowd, const uint8_t* gt_ig, const int64_t* gt_cell_start, int64_t G,
+                   int64_t cells, int64_t K, const double* iou_thrs, int T, const double* area_rng, int max_det, uint8_t* matched, uint8_t* ignored,
+                   int32_t* rank, int64_t* npig, mtp_stream_t stream);
+/* COCOeval.accumulate.  order (D): list positions category by category, inside a category by descending score (stable over the list order);
+ * cls_start (K + 1); score (D) f32 by list position; npig (K, A) an INPUT (summed over the ranks).  max_dets: M HOST ints; rec_thrs:
+ * MTP_COCO_REC_THRS HOST doubles.  Per (k, a, m, t) over the detections of rank < max_dets[m]: tp = cumsum(matched & !ignored), fp = cumsum(!matched &
+ * !ignored) exact; rc = tp / npig, pr = tp / (fp + tp + 2^-52), pr made non-increasing from the right; precision (T, 101, K, A, M) / scores (same
+ * shape) f64 at the first position with rc >= rec_thrs[r], 0 where none; recall (T, K, A, M) = the last rc, 0 without detections.  npig = 0: all -1. */
+int mtp_coco_accumulate(const uint8_t* matched, const uint8_t* ignored, const int32_t* rank, const float* score, const int64_t* order,
+                        const int64_t* cls_start, const int64_t* npig, int64_t D, int64_t K, int T, const int32_t* max_dets, int M,
+                        const double* rec_thrs, double* precision, double* scores, double* recall, mtp_stream_t stream);
+
 /* ---- the oriented RPN (csrc/rpn.hip): anchors, the midpoint-offset coder (mmrotate's MidpointOffsetCoder, 'le90'), targets + loss, proposals.
  * f32 boxes and logits, int64 indices; no float atomics, two calls on the same inputs give the same bits.  The maps of a level are addressed by
  * element strides (image, channel, y, x): cls channel a, reg channel a * 6 + j for anchor a of A.  The levels tile the flat multi-level anchor

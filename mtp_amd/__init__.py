@@ -52,7 +52,7 @@ from .necks import FeatureFusionNeck, GlobalAveragePooling  # noqa: F401
 from .cls_heads import LinearClsHead  # noqa: F401
 from .classifiers import ImageClassifier  # noqa: F401
 from .segmentors import EncoderDecoder, SiamEncoderDecoder  # noqa: F401
-from .evaluation import Accuracy, DOTAMetric, IoUMetric, eval_rbbox_map  # noqa: F401
+from .evaluation import Accuracy, CocoMetric, DOTAMetric, IoUMetric, eval_coco, eval_rbbox_map  # noqa: F401
 from .ops_box import batched_nms, bbox_overlaps, box_iou_rotated, nms, nms_rotated  # noqa: F401
 from .task_modules import (AnchorGenerator, AssignResult, BboxOverlaps2D, MidpointOffsetCoder, MTP_RD_MaxIoUAssigner, MaxIoUAssigner,  # noqa: F401
                            RandomSampler, RBbox2HBboxOverlaps2D, RBboxOverlaps2D)

@@ -38,6 +38,9 @@ ASSIGN_BOX, ASSIGN_RBOX2HBOX, ASSIGN_ROTATED = 0, 1, 2
 # csrc/det_eval.hip: MTP_DET_MAX_THRS / MTP_DET_MAX_CLASSES / MTP_DET_AP_POINTS and enum mtp_det_ap_mode
 DET_MAX_THRS, DET_MAX_CLASSES, DET_AP_POINTS = 8, 4096, 11
 DET_AP_11POINTS, DET_AP_AREA = 0, 1
+# csrc/coco_eval.hip: MTP_COCO_MAX_THRS / _AREAS / _MAX_DET_LEVELS / _MAX_CLASSES / _REC_THRS / _MAX_CELL_GTS and enum mtp_coco_kind
+COCO_MAX_THRS, COCO_AREAS, COCO_MAX_DET_LEVELS, COCO_MAX_CLASSES, COCO_REC_THRS, COCO_MAX_CELL_GTS = 16, 4, 4, 4096, 101, 4096
+COCO_BBOX, COCO_SEGM = 0, 1
 
 # enum mtp_hroi_target (mtp_hroi_loss, csrc/hbox_head.hip)
 HROI_TARGET_ONES, HROI_TARGET_ENCODED = 0, 1
@@ -239,6 +242,10 @@ SIGNATURES = {
     "mtp_det_match": (i32, [p, p, p, p, i64, p, p, p, p, i64, i64, C.POINTER(f32), i32, p, p, p, i64, p]),
     "mtp_det_tpfp": (i32, [p, p, p, i64, p, p, i64, C.POINTER(f32), i32, p, i64, p, p, p]),
     "mtp_det_ap": (i32, [p, p, p, p, i64, i64, i32, i32, C.POINTER(C.c_double), p, p, p, p, p, p]),
+    "mtp_mask_pack": (i32, [p, i64, i64, p, p, p]),
+    "mtp_coco_iou": (i32, [i32, p, p, p, p, i64, p, p, p, p, p, i64, i64, i32, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), p, p, i64, p]),
+    "mtp_coco_match": (i32, [p, i64, p, p, p, i64, p, p, p, p, p, i64, i64, i64, C.POINTER(C.c_double), i32, C.POINTER(C.c_double), i32, p, p, p, p, p]),
+    "mtp_coco_accumulate": (i32, [p, p, p, p, p, p, p, i64, i64, i32, C.POINTER(i32), i32, C.POINTER(C.c_double), p, p, p, p]),
     "mtp_rpn_anchors": (i32, [p, i64, i64, i64, i64, i64, i64, i64, i64, i64, f32, p, p, p]),
     "mtp_rpn_loss_workspace_bytes": (i64, [i64, i64]),
     "mtp_rpn_loss": (i32, [C.POINTER(RpnLevel), i32, i64, p, i64, p, i64, p, p, p, p, i64, i64, C.POINTER(f32), C.POINTER(f32), f32, f32, f32, p, p, p, i64, p]),

@@ -15,6 +15,7 @@
 //              reference's dtypes, metric.py:342-346).  '11points': eleven running maxima of precision over recall >= point_k (a maximum is
 //              order-free), summed in ascending k and divided by 11 in float32: bit-equal to average_precision.  'area': a second, reverse walk
 //              with a running suffix maximum, sum over the true positives of (r_i - r_{i-1}) * suffixmax_i in float64 in a fixed order.
+#include "block_scan.h"
 #include "common.h"
 #include "rbox_geom.h"
 
@@ -111,25 +112,7 @@ __global__ void __launch_bounds__(kThreads) det_tpfp_kernel(const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------------------------------- average precision
-// inclusive sum over the workgroup's 256 threads, in thread order; total = the sum of all.  wsum: kThreads / MTP_WAVE words of LDS.
-__device__ __forceinline__ unsigned long long block_scan_add(unsigned long long v, unsigned long long* wsum, int tid, unsigned long long& total) {
-    const int lane = tid & (MTP_WAVE - 1), w = tid / MTP_WAVE;
-    for (int off = 1; off < MTP_WAVE; off <<= 1) {
-        const unsigned long long o = __shfl_up(v, off);
-        if (lane >= off) v += o;
-    }
-    __syncthreads();      // the readers of the previous call are done with wsum
-    if (lane == MTP_WAVE - 1) wsum[w] = v;
-    __syncthreads();
-    unsigned long long before = 0ull, all = 0ull;
-    for (int i = 0; i < kThreads / MTP_WAVE; ++i) {
-        if (i < w) before += wsum[i];
-        all += wsum[i];
-    }
-    total = all;
-    return v + before;
-}
-
+// (block_scan_add, the exact inclusive sum in thread order, is block_scan.h)
 // max over the threads tid .. 255 (a suffix maximum, order-free); total = the maximum of all
 __device__ __forceinline__ float block_suffix_max(float v, float* wmax, int tid, float& total) {
     const int lane = tid & (MTP_WAVE - 1), w = tid / MTP_WAVE;

@@ -1579,6 +1579,186 @@ def det_ap(flags, order, cls_start, num_gts, mode="11points", curves=False, out=
     return ap, num_dets, last_recall, recall, precision
 
 
+# ------------------------------------------------------------------------------------------------ COCO-style metric (csrc/coco_eval.hip)
+COCO_MAX_THRS, COCO_AREAS, COCO_MAX_DET_LEVELS, COCO_MAX_CLASSES = _lib.COCO_MAX_THRS, _lib.COCO_AREAS, _lib.COCO_MAX_DET_LEVELS, _lib.COCO_MAX_CLASSES
+COCO_REC_THRS, COCO_MAX_CELL_GTS = _lib.COCO_REC_THRS, _lib.COCO_MAX_CELL_GTS
+COCO_KIND = {"bbox": _lib.COCO_BBOX, "segm": _lib.COCO_SEGM}
+COCO_MAX_DETS = (1 << 31) - 1
+# COCOeval.Params.areaRng (all, small, medium, large; both ends inclusive) and recThrs
+COCO_AREA_RNG = ((0.0, 1e5 ** 2), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, 1e5 ** 2))
+COCO_REC_POINTS = tuple([i * (1.0 / 100) for i in range(100)] + [1.0])      # np.linspace(0, 1, 101) bit for bit: i * step, the last one the stop
+
+
+def _i64s(values):
+    return (C.c_int64 * len(values))(*[int(v) for v in values])
+
+
+def _f64s(values):
+    return (C.c_double * len(values))(*[float(v) for v in values])
+
+
+def mask_pack(masks, words=None, areas=None):
+    """masks (N, H, W) or (N, H * W), bool or uint8 -> words (N, ceil(H * W / 64)) int64 (bit p of word w = pixel 64 w + p, the tail zero) and areas (N)
+    int64 (zeroed here).  One launch, no sync.  N may be 0."""
+    name = "mask_pack"
+    if masks.dtype not in (torch.bool, torch.uint8) or masks.dim() not in (2, 3):
+        raise TypeError("mask_pack: masks must be bool or uint8 of shape (N, H, W) or (N, H * W), got %s %s" % (masks.dtype, tuple(masks.shape)))
+    N, HW = masks.shape[0], int(masks.shape[1:].numel())
+    if HW < 1:
+        raise ValueError("mask_pack: empty masks (H * W = 0)")
+    W, dev = (HW + 63) // 64, masks.device
+    words = _scratch((N, W), dev, torch.int64) if words is None else words
+    areas = _scratch((N,), dev, torch.int64).zero_() if areas is None else areas
+    _det_typed(name, "words", words, torch.int64, (N, W))
+    _det_typed(name, "areas", areas, torch.int64, (N,))
+    if N:
+        check(lib().mtp_mask_pack(_p(masks.view(torch.uint8) if masks.dtype == torch.bool else masks), N, HW, _p(words), _p(areas), _s()), "mtp_mask_pack")
+    return words, areas
+
+
+def coco_iou(kind, det, det_labels, gt, gt_labels, gt_crowd, det_start, gt_start, agnostic=False, iou=None, inter=None):
+    """kind 'bbox': det / gt = boxes (D, 4) / (G, 4) f32 x1, y1, x2, y2.  kind 'segm': det / gt = (words, areas) of mask_pack, the same word count.
+    labels int64, gt_crowd uint8.  det_start / gt_start: HOST sequences of n_img + 1 offsets, starting at 0, into the tables.  -> iou (sum D_i G_i) f64:
+    image i's row-major (D_i, G_i) block at out_start[i]; inter (same layout) int64 for 'segm' else None; out_start (list).  No sync."""
+    name = "coco_iou"
+    if kind not in COCO_KIND:
+        raise ValueError("coco_iou: kind must be 'bbox' or 'segm', got %r" % (kind,))
+    D, G = det_labels.shape[0], gt_labels.shape[0]
+    det_start, gt_start = [int(v) for v in det_start], [int(v) for v in gt_start]
+    n_img = len(det_start) - 1
+    if n_img < 0 or len(gt_start) != n_img + 1 or det_start[0] != 0 or gt_start[0] != 0 or det_start[-1] != D or gt_start[-1] != G:
+        raise ValueError("coco_iou: det_start / gt_start must hold images + 1 offsets from 0 to the table sizes (%d, %d)" % (D, G))
+    if any(b < a for a, b in zip(det_start, det_start[1:])) or any(b < a for a, b in zip(gt_start, gt_start[1:])):
+        raise ValueError("coco_iou: offsets must not decrease")
+    _det_typed(name, "det_labels", det_labels, torch.int64, (D,))
+    _det_gts(name, gt_labels, gt_crowd, G)
+    W, boxes, words = 0, (None, None), (None, None, None, None)
+    if kind == "bbox":
+        _check_boxes(name, det, 4)
+        _check_boxes(name, gt, 4)
+        if det.shape[0] != D or gt.shape[0] != G:
+            raise TypeError("coco_iou: %d / %d boxes for %d / %d labels" % (det.shape[0], gt.shape[0], D, G))
+        boxes = (det, gt)
+    else:
+        (dw, da), (gw, ga) = det, gt
+        W = dw.shape[1] if dw.dim() == 2 else -1
+        _det_typed(name, "det words", dw, torch.int64, (D, W))
+        _det_typed(name, "gt words", gw, torch.int64, (G, W))
+        _det_typed(name, "det areas", da, torch.int64, (D,))
+        _det_typed(name, "gt areas", ga, torch.int64, (G,))
+        if W < 1:
+            raise ValueError("coco_iou: masks without words")
+        words = (dw, da, gw, ga)
+    out_start = [0]
+    for i in range(n_img):
+        out_start.append(out_start[-1] + (det_start[i + 1] - det_start[i]) * (gt_start[i + 1] - gt_start[i]))
+    n, dev = out_start[-1], det_labels.device
+    iou = _scratch((n,), dev, torch.float64) if iou is None else iou
+    _det_typed(name, "iou", iou, torch.float64, (n,))
+    if kind == "segm":
+        inter = _scratch((n,), dev, torch.int64) if inter is None else inter
+        _det_typed(name, "inter", inter, torch.int64, (n,))
+    else:
+        inter = None
+    q = lambda t: _p(t) if (t is not None and t.numel()) else None      # noqa: E731
+    if n:
+        check(lib().mtp_coco_iou(COCO_KIND[kind], q(boxes[0]), q(words[0]), q(words[1]), q(det_labels), D, q(boxes[1]), q(words[2]), q(words[3]),
+                                 q(gt_labels), q(gt_crowd), G, W, int(bool(agnostic)), n_img, _i64s(det_start), _i64s(gt_start), _i64s(out_start), _p(iou),
+                                 q(inter), n, _s()), "mtp_coco_iou")
+    return iou, inter, out_start
+
+
+def _coco_thrs(name, iou_thrs):
+    thrs = [float(t) for t in iou_thrs]
+    if not 1 <= len(thrs) <= COCO_MAX_THRS:
+        raise ValueError("%s: 1 to %d IoU thresholds, got %d" % (name, COCO_MAX_THRS, len(thrs)))
+    return thrs
+
+
+def _coco_max_dets(name, max_dets):
+    mds = [int(m) for m in max_dets]
+    if not 1 <= len(mds) <= COCO_MAX_DET_LEVELS or any(m < 1 or m > COCO_MAX_DETS for m in mds):
+        raise ValueError("%s: 1 to %d positive maxDets, got %r" % (name, COCO_MAX_DET_LEVELS, mds))
+    return mds
+
+
+def coco_match(iou, det_row, det_area, det_cell_start, gt_order, gt_col, gt_crowd, gt_ig, gt_cell_start, num_classes, iou_thrs, max_det,
+               area_rng=COCO_AREA_RNG, max_cell_gts=0, out=None):
+    """COCOeval.evaluateImg on the tables of include/mtp_hip.h (mtp_coco_match): the (D) detection tables in list order (cell by cell, by descending
+    score), det_cell_start / gt_cell_start (cells + 1) with cells = images x num_classes, gt_order / gt_ig (4, G).  max_cell_gts: the caller's
+    host-known bound on the gts of one cell (the largest image's gt count), refused beyond COCO_MAX_CELL_GTS.  -> matched, ignored (4, T, D) uint8,
+    rank (D) int32, npig (K, 4) int64 (zeroed here).  One launch, no sync."""
+    name = "coco_match"
+    thrs, A = _coco_thrs(name, iou_thrs), COCO_AREAS
+    T, K, D, G, cells = len(thrs), int(num_classes), det_row.shape[0], gt_col.shape[0], det_cell_start.shape[0] - 1
+    if not 0 < K <= COCO_MAX_CLASSES or cells < 0 or cells % K:
+        raise ValueError("%s: 1 to %d classes and images x classes cells, got %d classes, %d cells" % (name, COCO_MAX_CLASSES, K, cells))
+    if int(max_cell_gts) > COCO_MAX_CELL_GTS:
+        raise ValueError("%s: %d gts in one image; at most %d per (image, category)" % (name, max_cell_gts, COCO_MAX_CELL_GTS))
+    if D > COCO_MAX_DETS or G > COCO_MAX_DETS or not 1 <= int(max_det) <= COCO_MAX_DETS:
+        raise ValueError("%s: at most 2^31 - 1 detections, gts and max_det" % name)
+    if len(area_rng) != A:
+        raise ValueError("%s: %d area ranges" % (name, A))
+    if iou.dtype != torch.float64 or iou.dim() != 1:
+        raise TypeError("%s: iou must be float64 of shape (n,)" % name)
+    _det_typed(name, "det_row", det_row, torch.int64, (D,))
+    _det_typed(name, "det_area", det_area, torch.float64, (D,))
+    _det_typed(name, "det_cell_start", det_cell_start, torch.int64, (cells + 1,))
+    _det_typed(name, "gt_cell_start", gt_cell_start, torch.int64, (cells + 1,))
+    _det_typed(name, "gt_order", gt_order, torch.int64, (A, G))
+    _det_typed(name, "gt_ig", gt_ig, torch.uint8, (A, G))
+    _det_typed(name, "gt_col", gt_col, torch.int64, (G,))
+    _det_typed(name, "gt_crowd", gt_crowd, torch.uint8, (G,))
+    dev = det_cell_start.device
+    if out is None:
+        out = (_scratch((A, T, D), dev, torch.uint8), _scratch((A, T, D), dev, torch.uint8), _scratch((D,), dev, torch.int32),
+               _scratch((K, A), dev, torch.int64).zero_())
+    matched, ignored, rank, npig = out
+    _det_typed(name, "matched", matched, torch.uint8, (A, T, D))
+    _det_typed(name, "ignored", ignored, torch.uint8, (A, T, D))
+    _det_typed(name, "rank", rank, torch.int32, (D,))
+    _det_typed(name, "npig", npig, torch.int64, (K, A))
+    q = lambda t: _p(t) if t.numel() else None      # noqa: E731
+    rng = _f64s([v for lo_hi in area_rng for v in lo_hi])
+    if cells:
+        check(lib().mtp_coco_match(q(iou), iou.numel(), q(det_row), q(det_area), _p(det_cell_start), D, q(gt_order), q(gt_col), q(gt_crowd), q(gt_ig),
+                                   _p(gt_cell_start), G, cells, K, _f64s(thrs), T, rng, int(max_det), q(matched), q(ignored), q(rank), _p(npig), _s()),
+              "mtp_coco_match")
+    return matched, ignored, rank, npig
+
+
+def coco_accumulate(matched, ignored, rank, score, order, cls_start, npig, max_dets, rec_thrs=COCO_REC_POINTS, out=None):
+    """COCOeval.accumulate: matched / ignored (4, T, D) uint8, rank (D) int32 and score (D) f32 by list position; order (D) int64: list positions
+    category by category, by descending score; cls_start (K + 1); npig (K, 4) int64.  -> precision (T, 101, K, 4, M) f64, scores (same shape) f64,
+    recall (T, K, 4, M) f64.  One launch, no sync.  D may be 0."""
+    name = "coco_accumulate"
+    mds, A, R = _coco_max_dets(name, max_dets), COCO_AREAS, COCO_REC_THRS
+    if matched.dtype != torch.uint8 or matched.dim() != 3 or matched.shape[0] != A:
+        raise TypeError("%s: matched must be uint8 of shape (4, T, D), got %s %s" % (name, matched.dtype, tuple(matched.shape)))
+    T, D, K, M = matched.shape[1], matched.shape[2], npig.shape[0], len(mds)
+    if not 1 <= T <= COCO_MAX_THRS or not 0 < K <= COCO_MAX_CLASSES or D > COCO_MAX_DETS:
+        raise ValueError("%s: 1 to %d thresholds, 1 to %d classes, at most 2^31 - 1 detections; got %d, %d, %d" % (name, COCO_MAX_THRS, COCO_MAX_CLASSES, T, K, D))
+    if len(rec_thrs) != R:
+        raise ValueError("%s: %d recall thresholds" % (name, R))
+    _det_typed(name, "ignored", ignored, torch.uint8, (A, T, D))
+    _det_typed(name, "rank", rank, torch.int32, (D,))
+    _det_typed(name, "score", score, torch.float32, (D,))
+    _det_typed(name, "order", order, torch.int64, (D,))
+    _det_typed(name, "cls_start", cls_start, torch.int64, (K + 1,))
+    _det_typed(name, "npig", npig, torch.int64, (K, A))
+    dev = npig.device
+    if out is None:
+        out = (_scratch((T, R, K, A, M), dev, torch.float64), _scratch((T, R, K, A, M), dev, torch.float64), _scratch((T, K, A, M), dev, torch.float64))
+    precision, scores, recall = out
+    _det_typed(name, "precision", precision, torch.float64, (T, R, K, A, M))
+    _det_typed(name, "scores", scores, torch.float64, (T, R, K, A, M))
+    _det_typed(name, "recall", recall, torch.float64, (T, K, A, M))
+    q = lambda t: _p(t) if t.numel() else None      # noqa: E731
+    check(lib().mtp_coco_accumulate(q(matched), q(ignored), q(rank), q(score), q(order), _p(cls_start), _p(npig), D, K, T, (C.c_int32 * M)(*mds), M,
+                                    _f64s(rec_thrs), _p(precision), _p(scores), _p(recall), _s()), "mtp_coco_accumulate")
+    return precision, scores, recall
+
+
 # ------------------------------------------------------------------------------------------------ oriented RPN (csrc/rpn.hip)
 RPN_MAX_LEVELS = _lib.RPN_MAX_LEVELS
 RPN_DELTAS = 6
